@@ -76,6 +76,26 @@ def recorded_igemm_traffic(lib_hash, views=8):
     return float(rec["hbm_bytes_per_eval"]), name
 
 
+DUMP_BYTES = 64 << 20                                         # --dump-outputs: budget of all ranks' files together
+
+
+def dump_outputs(out_dir, outs, rank, world):
+    """--dump-outputs: each host tensor of ``outs`` as out_dir/<name>.npy in float32 (<name>_rank<r> with several ranks).  A rank's
+    share of DUMP_BYTES is DUMP_BYTES / world; an output above it is written as a sample of its flattened elements at indices drawn
+    from a fixed seed (sorted), the same in every run and every build, so that two dumps compare element for element"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // world // max(len(outs), 1) // 4
+    for name, x in outs.items():
+        x = x.float()
+        if x.numel() > budget:
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:budget].sort().values
+            x = x.reshape(-1)[idx]
+        fn = os.path.join(out_dir, "%s%s.npy" % (name, "" if world == 1 else "_rank%d" % rank))
+        np.save(fn, x.numpy())
+        print("bench.py: wrote %s %s" % (fn, list(x.shape)), file=sys.stderr, flush=True)
+
+
 class RegionGuard:
     """wall-clock bound on a region that contains collectives: a rank stuck in `Work.wait()` / a barrier past `limit_s` runs
     `on_expire()` (rank 0: print what has been measured) and leaves the process with `code` -- from a timer thread, through
@@ -211,7 +231,13 @@ def main():
                          "with the pinned tuner table in force)")
     ap.add_argument("--controlnets", action="store_true",
                     help="attach the depth + normal ControlNet pair driven by the G-buffers (BASELINE config 4's composition)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed calls, write what the last of them returned (the decoded frames, float32) to DIR/frames.npy "
+                         "(DIR/frames_rankR.npy per rank with more than one); inputs are seeded, so the same arguments give the same "
+                         "inputs in every run.  Above %d MB in all, a fixed seeded sample of the elements is written" % (DUMP_BYTES >> 20))
     a = ap.parse_args()
+    if a.dump_outputs is not None and (a.steps < 1 or a.roofline_only):
+        ap.error("--dump-outputs needs timed calls (--steps >= 1, no --roofline-only)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("SR_SHARD_FORCE") != "1":
         sys.exit(launch_ranks(a, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -479,7 +505,7 @@ def main():
                 sync()
                 note("timed region: %d calls, %d in flight" % (a.steps, inflight))
                 t0 = time.perf_counter()
-                fl.run(a.steps)                               # exactly K calls, call c on slot c % inflight
+                last = fl.run(a.steps)                        # exactly K calls, call c on slot c % inflight
                 sync()
             else:
                 note("warm-up: %d call(s) (plans built and captured here)" % a.warmup)
@@ -491,9 +517,11 @@ def main():
                 note("timed region: %d calls, one at a time" % a.steps)
                 t0 = time.perf_counter()
                 for _ in range(a.steps):
-                    pipe.call()
+                    last = pipe.call()
                 sync()
             dt = max(time.perf_counter() - t0, 1e-9)
+            # the last timed call's frames live in a buffer the calls below overwrite: copied to the host now
+            outs = {"frames": last.cpu()} if a.dump_outputs is not None else None
             comm_ms = pipe.runner.exposed_comm_ms() if shard is not None else None     # compute-stream stalls in the K/V-source waits
             dt = max_over_ranks(dt)
             frames = a.views * a.steps * (1 if shard is not None else world)
@@ -531,13 +559,15 @@ def main():
                 fl2.warm(max(1, a.warmup))
                 sync()
                 t2 = time.perf_counter()
-                fl2.run(a.steps)
+                last = fl2.run(a.steps)
                 sync()
                 dt2 = max_over_ranks(max(time.perf_counter() - t2, 1e-9))
                 shard_inflight = {"value": round(frames / dt2, 4), "ms_per_step": round(dt2 / max(a.steps, 1) * 1e3, 2),
                                   "calls_in_flight_per_gpu": a.inflight}
                 if dt2 < dt:                                  # the headline keeps calls in flight, as at N = 1
                     one_at_a_time, dt, inflight, comm_ms = frames / dt, dt2, a.inflight, None
+                    if outs is not None:
+                        outs = {"frames": last.cpu()}
             if dist is not None:
                 sync()                                        # every rank has finished its sharded phase before the line goes out
     except Exception as e:                                    # noqa: BLE001 -- a failing sharded phase must not cost the line
@@ -552,6 +582,8 @@ def main():
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         note("CPU baseline: the oracle on a bounded sample of the same workload")
         cpu = cpu_baseline()
+    if a.dump_outputs is not None:
+        dump_outputs(a.dump_outputs, outs, rank, world)
     note("done")
     if rank == 0:
         out = line(frames / dt, dt, a.steps, shard, inflight, comm_ms, one_at_a_time, replicas, check, roof, cpu)

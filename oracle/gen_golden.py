@@ -421,7 +421,9 @@ def sec_sdxl():
         yv = rnd(7, 2, 192)
         y = m(x, t, context=ctx, y=yv, transformer_options={})
         save("unet_sdxl_tiny", x=x, t=t, ctx=ctx, yvec=yv, y=y)
-        # SDXL.encode_adm itself (comfy/model_base.py:352-369) on a stub that only carries the 256-wide Timestep embedder
+        # SDXL.encode_adm itself (comfy/model_base.py:352-369) on a stub that only carries the 256-wide Timestep embedder.
+        # Its exp / sin / cos go through MKL's vector maths: the adm_* vectors are made with MKL_CBWR=COMPATIBLE in the environment
+        # (the same bits on every x86 CPU; the host test evaluates its side the same way)
         import types
         import comfy.model_base as mb
         from comfy.ldm.modules.diffusionmodules.openaimodel import Timestep

@@ -180,11 +180,13 @@ class InflightCalls:
             p.frame0 = f
 
     def run(self, n_calls):
-        """n_calls calls, call c handled by slot c % K -> list of per-call outputs is not kept (the corr-map is the product);
-        returns after every stream has drained"""
+        """n_calls calls, call c handled by slot c % K; returns after every stream has drained, with the decoded frames of the
+        LAST call (its slot's output buffer: valid until that slot's next call) -- earlier calls' frames are not kept (the
+        corr-map is the product)"""
         base = self.pipes[0].frame0
         order = CallOrder()
         errs = []
+        last = []
         torch.cuda.synchronize()
 
         def work(i):
@@ -194,7 +196,9 @@ class InflightCalls:
                 with torch.cuda.stream(st), O.workspace_slot(i):
                     for c in range(i, n_calls, len(self.pipes)):
                         p.frame0 = base + c * p.N_all
-                        p.call(order=(order, c))
+                        img = p.call(order=(order, c))
+                        if c == n_calls - 1:
+                            last.append(img)
                     st.synchronize()
             except BaseException as e:                      # noqa: BLE001 - re-raised on the caller's thread
                 errs.append(e)
@@ -208,6 +212,7 @@ class InflightCalls:
             raise errs[0]
         for p in self.pipes:
             p.frame0 = base + n_calls * p.N_all
+        return last[0] if last else None
 
 
 class FramePipeline:

@@ -190,14 +190,24 @@ def test_call_order_tickets_serialize_sections_in_call_order():
     assert not tw.is_alive() and seen == ["raised", "another in-flight call failed"]
 
 
-def test_sdxl_encode_adm_matches_the_reference():
-    """sampling.encode_adm_sdxl vs comfy SDXL.encode_adm itself (golden sdxl_adm.npz, made by oracle/gen_golden.py sdxl)"""
-    from stable_renderer_amd.sampling import encode_adm_sdxl
-    d = np.load(os.path.join(GOLD, "sdxl_adm.npz"))
-    pooled = torch.from_numpy(d["pooled"])
-    assert torch.equal(encode_adm_sdxl(pooled, 1024, 1024), torch.from_numpy(d["adm_default"]))
-    got = encode_adm_sdxl(pooled, 832, 1216, crop_w=8, crop_h=16, target_width=1024, target_height=1024)
-    assert torch.equal(got, torch.from_numpy(d["adm_custom"])) and tuple(got.shape) == (2, 2816)
+def test_sdxl_encode_adm_matches_the_reference(tmp_path):
+    """sampling.encode_adm_sdxl vs comfy SDXL.encode_adm itself (golden sdxl_adm.npz, made by oracle/gen_golden.py sdxl), bit for
+    bit.  exp / sin / cos of a CPU tensor run through MKL's vector maths, whose last bits depend on the code path MKL picks for the
+    CPU at hand; both sides are evaluated with MKL_CBWR=COMPATIBLE, the mode that gives the same bits on every x86 CPU.  MKL reads
+    it once per process, hence the child process."""
+    code = ("import sys\nsys.path.insert(0, %r)\nimport numpy as np, torch\n"
+            "from stable_renderer_amd.sampling import encode_adm_sdxl\n"
+            "pooled = torch.from_numpy(np.load(%r)['pooled'])\n"
+            "np.savez(%r, default=encode_adm_sdxl(pooled, 1024, 1024).numpy(),\n"
+            "         custom=encode_adm_sdxl(pooled, 832, 1216, crop_w=8, crop_h=16, target_width=1024, target_height=1024).numpy())\n"
+            % (ROOT, os.path.join(GOLD, "sdxl_adm.npz"), str(tmp_path / "adm.npz")))
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MKL_CBWR="COMPATIBLE"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    d, got = np.load(os.path.join(GOLD, "sdxl_adm.npz")), np.load(tmp_path / "adm.npz")
+    assert torch.equal(torch.from_numpy(got["default"]), torch.from_numpy(d["adm_default"]))
+    assert torch.equal(torch.from_numpy(got["custom"]), torch.from_numpy(d["adm_custom"])) and got["custom"].shape == (2, 2816)
 
 
 def test_latent_scale_follows_the_model_family():
