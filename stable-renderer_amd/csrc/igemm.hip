@@ -542,9 +542,20 @@ __device__ __forceinline__ void igemm_body(const sr_igemm_args& p, const int M, 
   // instructions per fragment and k-substep beside 10..40 MFMAs.
   constexpr int TMS = LNI ? TM / WAVES_N : 1;
   static_assert(!LNI || (TM % WAVES_N == 0 && !SPLIT), "in-launch LayerNorm statistics: fragments split evenly over the waves of a row block");
-  float lsum[TMS], lsq[TMS];
+  // fp32 sums are of x - pivot, the pivot being the row's first element (rows past M are zero-page rows: pivot 0): plain sums of x
+  // and x^2 cancel in var = E[x^2] - mean^2 when the row mean is large against its spread (mean / std = 30 lost the fp32 bound),
+  // shifted sums only by (x0 - mean)^2 / var.  (The fp16 form, v_dot2 on packed halves, stays unshifted: its error is far below
+  // the fp16 output's resolution there.)
+  float lsum[TMS], lsq[TMS], lpiv[TMS];
 #pragma unroll
-  for (int i = 0; i < TMS; ++i) { lsum[i] = 0.f; lsq[i] = 0.f; }
+  for (int i = 0; i < TMS; ++i) {
+    lsum[i] = 0.f; lsq[i] = 0.f; lpiv[i] = 0.f;
+    if constexpr (LNI && sizeof(T) == 4) {
+      const int m = m0 + pm0 + (wn + i * WAVES_N) * 16 + c16;
+      if (m < M) lpiv[i] = ((const float*)p.a)[(int64_t)m * C1];
+      asm volatile("" ::"v"(lpiv[i]));                     // consumed here: the load completes before the ring's LDS-DMA is issued
+    }
+  }
   auto ln_acc = [&](const char* tP, const int fo) {          // tP: this wave's row block of the X stage
 #pragma unroll
     for (int i = 0; i < TMS; ++i) {
@@ -558,7 +569,8 @@ __device__ __forceinline__ void igemm_body(const sr_igemm_args& p, const int M, 
         lsum[i] = __builtin_amdgcn_fdot2(h2, one, lsum[i], false); lsq[i] = __builtin_amdgcn_fdot2(h2, h2, lsq[i], false);
         lsum[i] = __builtin_amdgcn_fdot2(h3, one, lsum[i], false); lsq[i] = __builtin_amdgcn_fdot2(h3, h3, lsq[i], false);
       } else {
-        const float f0 = __uint_as_float(x.x), f1 = __uint_as_float(x.y), f2 = __uint_as_float(x.z), f3 = __uint_as_float(x.w);
+        const float f0 = __uint_as_float(x.x) - lpiv[i], f1 = __uint_as_float(x.y) - lpiv[i];
+        const float f2 = __uint_as_float(x.z) - lpiv[i], f3 = __uint_as_float(x.w) - lpiv[i];
         lsum[i] += f0; lsum[i] += f1; lsum[i] += f2; lsum[i] += f3;
         lsq[i] = fmaf(f0, f0, lsq[i]); lsq[i] = fmaf(f1, f1, lsq[i]); lsq[i] = fmaf(f2, f2, lsq[i]); lsq[i] = fmaf(f3, f3, lsq[i]);
       }
@@ -686,7 +698,8 @@ __device__ __forceinline__ void igemm_body(const sr_igemm_args& p, const int M, 
       su += __shfl_xor(su, 32); sq += __shfl_xor(sq, 32);
       const int tm = wn + i * WAVES_N;
       if (g4 == 0) {
-        const float mean = su * invk, var = fmaxf(fmaf(-mean, mean, sq * invk), 0.f);
+        const float dm = su * invk, var = fmaxf(fmaf(-dm, dm, sq * invk), 0.f);
+        const float mean = sizeof(T) == 4 ? lpiv[i] + dm : dm;
         const float rstd = rsqrtf(var + p.ln_eps);
         *(float2*)(smem_all + 8 * (pm0 + tm * 16 + c16)) = make_float2(rstd, -rstd * mean);
       }

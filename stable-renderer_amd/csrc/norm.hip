@@ -3,9 +3,12 @@
 // GroupNorm: pass 1 accumulates per-channel sum / sum-of-squares in registers (every thread owns a fixed
 // 16-byte channel chunk and walks pixels, so loads are fully coalesced along C), folds them to the 32 groups
 // in LDS and writes one fp32 partial per (batch, pixel-chunk, group) — no float atomics, so results are
-// bit-reproducible.  Pass 2 reduces the partials of its batch entry in a fixed order, builds per-channel
-// scale/shift in LDS and applies y = x*sc + sh (+SiLU).  Both passes can read the channel concat of two
-// sources, which is how the decoder's th.cat([h, skip]) is consumed without materialising it.
+// bit-reproducible.  The sums are of x - pivot, the pivot being the group's first element (pixel 0, first channel
+// of the group): plain sums of x and x^2 would cancel in var = E[x^2] - mean^2 when the mean is large against the
+// spread (mean / std = 30 lost the fp32 tolerance), shifted sums only by (x0 - mean)^2 / var.  Pass 2 reduces the
+// partials of its batch entry in a fixed order, builds per-channel scale/shift in LDS and applies y = x*sc + sh
+// (+SiLU).  Both passes can read the channel concat of two sources, which is how the decoder's th.cat([h, skip]) is
+// consumed without materialising it.
 #include "sr_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -45,7 +48,13 @@ __device__ __forceinline__ void store_chunk(T* p, const float (&v)[sr_traits<T>:
   }
 }
 
-// grid (nchunk, B), block 256.  partials[b][chunk][group][2]
+// the shift of the two-pass GroupNorm's sums: element (pixel 0, channel c0) of batch entry b, c0 the first channel of a group
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const T* x1, const T* x2, int b, int HW, int C1, int C2, int c0) {
+  return c0 < C1 ? (float)x1[(int64_t)b * HW * C1 + c0] : (float)x2[(int64_t)b * HW * C2 + (c0 - C1)];
+}
+
+// grid (nchunk, B), block 256.  partials[b][chunk][group][2]: sums of (x - pivot) and (x - pivot)^2
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x1, const T* __restrict__ x2, float* __restrict__ partials,
                                                        int HW, int C1, int C2, int groups, int nchunk) {
@@ -70,6 +79,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x1,
       const int c0 = cc * EPC;
       const T* src = c0 < C1 ? x1 + (int64_t)b * HW * C1 + c0 : x2 + (int64_t)b * HW * C2 + (c0 - C1);
       const int cs = c0 < C1 ? C1 : C2;
+      float piv[EPC];
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) piv[e] = gn_pivot<T>(x1, x2, b, HW, C1, C2, (c0 + e) / cpg * cpg);
       // four pixels per trip: four independent 16-byte loads in flight per lane (the walk is otherwise one load, a dependent
       // accumulate, the next load); the accumulation order per lane is unchanged, so results are too
       int p = p0 + ps;
@@ -81,17 +93,18 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x1,
         load_chunk<T>(src + (int64_t)(p + 3 * pp) * cs, v3);
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
-          s[e] += v0[e]; q[e] += v0[e] * v0[e];
-          s[e] += v1[e]; q[e] += v1[e] * v1[e];
-          s[e] += v2[e]; q[e] += v2[e] * v2[e];
-          s[e] += v3[e]; q[e] += v3[e] * v3[e];
+          const float d0 = v0[e] - piv[e], d1 = v1[e] - piv[e], d2 = v2[e] - piv[e], d3 = v3[e] - piv[e];
+          s[e] += d0; q[e] += d0 * d0;
+          s[e] += d1; q[e] += d1 * d1;
+          s[e] += d2; q[e] += d2 * d2;
+          s[e] += d3; q[e] += d3 * d3;
         }
       }
       for (; p < p1; p += pp) {
         float v[EPC];
         load_chunk<T>(src + (int64_t)p * cs, v);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { s[e] += v[e]; q[e] += v[e] * v[e]; }
+        for (int e = 0; e < EPC; ++e) { const float d = v[e] - piv[e]; s[e] += d; q[e] += d * d; }
       }
 #pragma unroll
       for (int e = 0; e < EPC; ++e) { chs[ps * C + c0 + e] = s[e]; chq[ps * C + c0 + e] = q[e]; }
@@ -104,11 +117,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x1,
       const int c0 = cc * EPC;
       const T* src = c0 < C1 ? x1 + (int64_t)b * HW * C1 + c0 : x2 + (int64_t)b * HW * C2 + (c0 - C1);
       const int cs = c0 < C1 ? C1 : C2;
+      float piv[EPC];
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) piv[e] = gn_pivot<T>(x1, x2, b, HW, C1, C2, (c0 + e) / cpg * cpg);
       for (int p = p0; p < p1; ++p) {
         float v[EPC];
         load_chunk<T>(src + (int64_t)p * cs, v);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { s[e] += v[e]; q[e] += v[e] * v[e]; }
+        for (int e = 0; e < EPC; ++e) { const float d = v[e] - piv[e]; s[e] += d; q[e] += d * d; }
       }
 #pragma unroll
       for (int e = 0; e < EPC; ++e) { chs[c0 + e] = s[e]; chq[c0 + e] = q[e]; }
@@ -182,10 +198,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
       double s = 0.0, q = 0.0;
       for (int p8 = 0; p8 < 8; ++p8) { s += red[(p8 * groups + tid) * 2]; q += red[(p8 * groups + tid) * 2 + 1]; }
       const double cnt = (double)HW * cpg;
-      const double mean = s / cnt;
-      double var = q / cnt - mean * mean;
+      const double dm = s / cnt;                     // mean of x - pivot
+      double var = q / cnt - dm * dm;
       if (var < 0.0) var = 0.0;
-      gm[tid] = (float)mean;
+      gm[tid] = (float)((double)gn_pivot<T>(x1, x2, b, HW, C1, C2, tid * cpg) + dm);
       gm[groups + tid] = (float)(1.0 / sqrt(var + (double)eps));
     }
   }
@@ -230,7 +246,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
 // channels, a multiple of one 16-byte chunk, contiguous per pixel), reads its slab ONCE into registers, reduces mean and
 // then the centred second moment through LDS in a fixed order (bit-reproducible, no E[x^2]-mean^2 cancellation), and
 // writes y = (x-mean)*rstd*gamma+beta (+SiLU).  One read + one write of the tensor and one launch instead of two reads,
-// a write, a partials round trip and two launches; the two-pass kernels above remain for large maps (VAE).
+// a write, a partials round trip and two launches; the two-pass kernels above remain for large maps (VAE).  Every moment is of
+// x - pivot (the group's first element): the fp32 mean of rows whose mean is 30 standard deviations from zero, and y formed as
+// x * scale + shift, each lost more than the fp32 tolerance to rounding.
 template <typename T, int NV, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void gn_fused_kernel(const T* __restrict__ x1, const T* __restrict__ x2, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, T* __restrict__ y, int HW, int C1, int C2,
@@ -253,9 +271,9 @@ __global__ __launch_bounds__(BLOCK) void gn_fused_kernel(const T* __restrict__ x
   const T* src = c0 < C1 ? x1 + (int64_t)b * HW * C1 + c0 : x2 + (int64_t)b * HW * C2 + (c0 - C1);
   const int cs = c0 < C1 ? C1 : C2;
   VEC raw[NV];
-  float acc[EPC];
+  float acc[EPC], piv[EPC];                         // sums of x - pivot (the group's first element, as in gn_stats_kernel)
 #pragma unroll
-  for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
+  for (int e = 0; e < EPC; ++e) { acc[e] = 0.f; piv[e] = gn_pivot<T>(x1, x2, b, HW, C1, C2, (c0 + e) / cpg * cpg); }
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int p = ps + i * pp;
@@ -264,11 +282,11 @@ __global__ __launch_bounds__(BLOCK) void gn_fused_kernel(const T* __restrict__ x
       float v[EPC];
       load_chunk<T>((const T*)&raw[i], v);
 #pragma unroll
-      for (int e = 0; e < EPC; ++e) acc[e] += v[e];
+      for (int e = 0; e < EPC; ++e) acc[e] += v[e] - piv[e];
     }
   }
   const float inv_cnt = 1.0f / ((float)HW * (float)cpg);
-  float mean_e[EPC], rstd_e[EPC];
+  float mean_e[EPC], rstd_e[EPC];                  // mean_e: mean of x - pivot
   // two rounds of the same fixed-order reduction: sum -> mean, centred squares -> rstd
   for (int round = 0; round < 2; ++round) {
     if (active) {
@@ -310,7 +328,7 @@ __global__ __launch_bounds__(BLOCK) void gn_fused_kernel(const T* __restrict__ x
           asm volatile("" : "+v"(r));                // keep the slab packed in registers: no hoisted fp32 copies
           load_chunk<T>((const T*)&r, v);
 #pragma unroll
-          for (int e = 0; e < EPC; ++e) { const float d = v[e] - mean_e[e]; acc[e] += d * d; }
+          for (int e = 0; e < EPC; ++e) { const float d = (v[e] - piv[e]) - mean_e[e]; acc[e] += d * d; }
         }
       }
       __syncthreads();                               // gstat is rewritten by the next round
@@ -337,7 +355,7 @@ __global__ __launch_bounds__(BLOCK) void gn_fused_kernel(const T* __restrict__ x
       load_chunk<T>((const T*)&r, v);
 #pragma unroll
       for (int e = 0; e < EPC; ++e) {
-        const float t = v[e] * sc[e] + sh[e];
+        const float t = (v[e] - piv[e]) * sc[e] + sh[e];     // (x - pivot - mean') * rstd * gamma + beta
         v[e] = silu ? sr_silu_f(t) : t;
       }
       store_chunk<T>(dst + (int64_t)p * C, v);
