@@ -608,7 +608,9 @@ __global__ __launch_bounds__(NTHR, MB) void attn_pipe_kernel(const sr_attention_
       if (__any(moved)) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-          alpha[qt] = __builtin_amdgcn_exp2f(-delta[qt]);
+          // only the first tile moves the shift down (from 0), and then O and l are still 0: a first tile whose maximum lies
+          // below -128 would make exp2(-delta) = inf and 0 * inf = NaN
+          alpha[qt] = __builtin_amdgcn_exp2f(fminf(-delta[qt], 0.f));
 #pragma unroll
           for (int kt = 0; kt < KTB; ++kt) { sc[kt][qt][0] -= delta[qt]; sc[kt][qt][1] -= delta[qt]; sc[kt][qt][2] -= delta[qt]; sc[kt][qt][3] -= delta[qt]; }
           // channel d of the Q fragment = -m: rewritten in the lanes that hold it
@@ -877,7 +879,7 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn32_kernel(const sr_atten
       const float mnew = (float)(_Float16)(mrow + mx);       // fp16 representable: the MFMA sees exactly this value
       const float dl = mnew - mrow;
       mrow = mnew;
-      const float alpha = __builtin_amdgcn_exp2f(-dl);
+      const float alpha = __builtin_amdgcn_exp2f(fminf(-dl, 0.f));   // a downward move is the first tile's, onto O = 0 (no inf)
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
