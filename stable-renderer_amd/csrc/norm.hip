@@ -423,7 +423,7 @@ __global__ __launch_bounds__(BLOCK) void gn_wave_kernel(const T* __restrict__ x1
     if (active && p < HW) raw[i] = *(const VEC*)(src + (int64_t)p * cs);
   }
   for (int c = tid; c < span; c += BLOCK) { aff[0][c] = gamma[bundle * span + c]; aff[1][c] = beta[bundle * span + c]; }   // (visible after the barriers below)
-  // the thread's 8 (4) channels lie in at most two groups (cpg >= EPC / 2): g0 and, from element eb on, g0 + 1
+  // the thread's 8 (4) channels lie in at most two groups (try_gn_wave checks every chunk of the bundle): g0 and, from element eb on, g0 + 1
   const int g0 = cl / cpg, eb = (g0 + 1) * cpg - cl;
   const float inv_cnt = 1.0f / ((float)HW * (float)cpg);
   float mean0 = 0.f, mean1 = 0.f, rstd0 = 0.f, rstd1 = 0.f;
@@ -507,7 +507,11 @@ bool try_gn_wave(const sr_groupnorm_args* a, hipStream_t st) {
     if ((g * cpg) % EPC == 0 && a->groups % g == 0) { GB = g; break; }
   if (!GB) return false;
   const int vpp = GB * cpg / EPC;
-  if (vpp > 64 || GB * cpg > 512 || 2 * cpg < EPC) return false;      // (a thread's chunk may straddle two groups, not more)
+  if (vpp > 64 || GB * cpg > 512) return false;
+  // a thread's chunk may straddle two groups, not more (the kernel folds it into g0 and g0 + 1): fp16 at 5 channels per group
+  // (GB 8) puts channels 8..15 in groups 1, 2 and 3 -- left to gn_fused / the two-pass kernels, which look up every element's group
+  for (int cl = 0; cl < GB * cpg; cl += EPC)
+    if ((cl + EPC - 1) / cpg - cl / cpg > 1) return false;
   static const int max_wg = getenv("SR_GN_WAVE_MAX_WG") ? atoi(getenv("SR_GN_WAVE_MAX_WG")) : 256;   // tuning / A-B aid (0 = off)
   if ((a->groups / GB) * a->B > max_wg) return false;
   auto need = [&](int block) { return sr_cdiv(a->HW, block / vpp); };
