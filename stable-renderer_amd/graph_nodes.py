@@ -325,19 +325,42 @@ class VAE:
     def __init__(self, decoder, encoder=None):
         self.decoder, self.encoder = decoder, encoder
         self._enc_plans = {}
+        self._dec_tile_plans, self._enc_tile_plans = {}, {}
 
     def __getattr__(self, name):
         return getattr(self.__dict__["decoder"], name)
 
-    def encode(self, pixels):
-        """pixels (N,H,W,C) in [0,1] -> (N,4,H/8,W/8) fp32; crops to a multiple of 8 as vae_encode_crop_pixels (sd.py:292-299)"""
+    def decode_tiled(self, samples, tile_x=64, tile_y=64, overlap=16):
+        """samples (N,4,h,w) -> (N,8h,8w,3) fp32 in [0,1] (sd.py:302-314, :348-351): three passes of feathered tiles (tile_x//2 x
+        tile_y*2, tile_x*2 x tile_y//2, tile_x x tile_y latents), blended and averaged on the GPU; no h*w x h*w score matrix larger
+        than a tile's is ever built.  Tile plans are cached per (N, th, tw)."""
+        from . import tiled
+        return tiled.decode_tiled(self.decoder, self._dec_tile_plans, samples, tile_x, tile_y, overlap)
+
+    def encode_tiled(self, pixels, tile_x=512, tile_y=512, overlap=64, noise=None):
+        """pixels (N,H,W,C) in [0,1] -> (N,4,H/8,W/8) fp32 (sd.py:316-327, :373-378); crops to a multiple of 8 as ``encode`` does.  The
+        posterior noise of every tile is drawn up front from the global CPU generator in the reference's order
+        (tiled.draw_encode_noise), or taken from ``noise``."""
         if self.encoder is None:
             raise ValueError("this VAE came without encoder weights (encoder.* / quant_conv keys)")
+        from . import tiled
+        return tiled.encode_tiled(self.encoder, self._enc_tile_plans, self._crop8(pixels), tile_x, tile_y, overlap, noise=noise)
+
+    @staticmethod
+    def _crop8(pixels):
+        """vae_encode_crop_pixels (sd.py:292-299)"""
         x = (pixels.shape[1] // 8) * 8
         y = (pixels.shape[2] // 8) * 8
         if pixels.shape[1] != x or pixels.shape[2] != y:
             xo, yo = (pixels.shape[1] % 8) // 2, (pixels.shape[2] % 8) // 2
             pixels = pixels[:, xo:x + xo, yo:y + yo, :]
+        return pixels
+
+    def encode(self, pixels):
+        """pixels (N,H,W,C) in [0,1] -> (N,4,H/8,W/8) fp32; crops to a multiple of 8 as vae_encode_crop_pixels (sd.py:292-299)"""
+        if self.encoder is None:
+            raise ValueError("this VAE came without encoder weights (encoder.* / quant_conv keys)")
+        pixels = self._crop8(pixels)
         key = (pixels.shape[0], pixels.shape[1], pixels.shape[2])
         if key not in self._enc_plans:
             self._enc_plans[key] = self.encoder.build(*key)
@@ -358,6 +381,41 @@ class VAEEncode:
         if pixels.dim() == 3:
             pixels = pixels.unsqueeze(0)
         return (N.LATENT(samples=vae.encode(pixels[:, :, :, :3])),)
+
+
+class VAEEncodeTiled:
+    """comfyUI/nodes.py:334-347"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "encode"
+    CATEGORY = "_for_testing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"pixels": ("IMAGE",), "vae": ("VAE",),
+                             "tile_size": ("INT", {"default": 512, "min": 320, "max": 4096, "step": 64})}}
+
+    def encode(self, vae, pixels, tile_size=512):
+        return (N.LATENT(samples=vae.encode_tiled(pixels[:, :, :, :3], tile_x=tile_size, tile_y=tile_size)),)
+
+
+class VAEDecodeTiled:
+    """comfyUI/nodes.py:305-317.  A bare VAEDecoder (a checkpoint without encoder weights) is wrapped once; the wrapper, and with it
+    the tile plans, stays on the decoder object, so a fresh node instance per execution rebuilds nothing"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "decode"
+    CATEGORY = "_for_testing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "vae": ("VAE",),
+                             "tile_size": ("INT", {"default": 512, "min": 320, "max": 4096, "step": 64})}}
+
+    def decode(self, vae, samples, tile_size=512):
+        if not isinstance(vae, VAE):
+            if getattr(vae, "_tiled_vae", None) is None:
+                vae._tiled_vae = VAE(vae)
+            vae = vae._tiled_vae
+        return (vae.decode_tiled(samples["samples"], tile_x=tile_size // 8, tile_y=tile_size // 8),)
 
 
 class LoadImage:
@@ -432,7 +490,7 @@ class IfValTypeEqual(N.StableRenderingNode):
 
 for _name, _cls in (("CheckpointLoaderSimple", CheckpointLoaderSimple), ("LoraLoaderModelOnly", LoraLoaderModelOnly),
                     ("ControlNetLoader", ControlNetLoader), ("ControlNetApply", ControlNetApply), ("ControlNetApplyAdvanced", ControlNetApplyAdvanced), ("CLIPTextEncode", CLIPTextEncode),
-                    ("SceneTextEncode", SceneTextEncode), ("MaskedTextEncode", MaskedTextEncode), ("KSampler", KSampler), ("VAEDecode", VAEDecode), ("VAEEncode", VAEEncode), ("LoadImage", LoadImage),
+                    ("SceneTextEncode", SceneTextEncode), ("MaskedTextEncode", MaskedTextEncode), ("KSampler", KSampler), ("VAEDecode", VAEDecode), ("VAEEncode", VAEEncode), ("VAEDecodeTiled", VAEDecodeTiled), ("VAEEncodeTiled", VAEEncodeTiled), ("LoadImage", LoadImage),
                     ("IsNotNone", IsNotNone), ("If", If), ("IfValTypeEqual", IfValTypeEqual),
                     ("EngineData", N.EngineDataNode), ("VirtualEngineData", N.VirtualEngineDataNode),
                     ("InferenceOutput", N.InferenceOutputNode), ("EmptyCorrMaps", N.EmptyCorrMaps),

@@ -8,6 +8,7 @@ import threading
 import torch
 
 from . import _lib as L
+from . import _lib_tiled as LT
 
 DT = {torch.float16: L.SR_F16, torch.float32: L.SR_F32}
 TDT = {L.SR_F16: torch.float16, L.SR_F32: torch.float32}
@@ -627,3 +628,39 @@ def lcm_step(x, den, noise, sigma_next):
 
 def axpby(y, x, a, b):
     L.check(L.lib().sr_axpby(_p(y), _p(x), x.numel(), float(a), float(b), stream_ptr()))
+
+
+# ---- tiled VAE (libsr_tiled.so, include/sr_tiled.h) ---------------------------------------------------------------------------
+
+def softmax_rows_ld(x, rows, cols, ld):
+    """in-place softmax over the first `cols` entries of `rows` rows that are `ld` entries apart; [cols, ld) becomes 0"""
+    LT.check(LT.lib().sr_softmax_rows_ld(_p(x), rows, cols, ld, DT[x.dtype], stream_ptr()))
+
+
+def tile_gather(src, dst, y0, x0):
+    """dst (P..., th, tw) = src (P..., H, W)[..., y0:y0+th, x0:x0+tw]; fp32, contiguous (sr_tile_gather)"""
+    H, W = src.shape[-2:]
+    th, tw = dst.shape[-2:]
+    LT.check(LT.lib().sr_tile_gather(_p(src), _p(dst), src.numel() // (H * W), H, W, y0, x0, th, tw, stream_ptr()))
+
+
+def tile_accumulate(tile, acc, wsum, y0, x0, feather, nhwc):
+    """acc[window at (y0, x0)] += tile * feather mask, wsum[window] += mask numerator (sr_tile_accumulate).  nhwc: tile (B,th,tw,C) into
+    acc (B,H,W,C); else tile (B,C,th,tw) into acc (B,C,H,W).  wsum: (H,W) int64"""
+    if nhwc:
+        planes, (H, W, cpp), (th, tw) = acc.shape[0], acc.shape[1:], tile.shape[1:3]
+    else:
+        planes, (H, W), cpp, (th, tw) = acc.shape[0] * acc.shape[1], acc.shape[2:], 1, tile.shape[2:]
+    LT.check(LT.lib().sr_tile_accumulate(_p(tile), _p(acc), _p(wsum), planes, H, W, cpp, y0, x0, th, tw, feather, stream_ptr()))
+
+
+def tile_finish(accs, wsums, out, feather, nhwc, process_output):
+    """out = mean over the passes of acc / (wsum / feather^4); process_output: then clamp((x+1)/2, 0, 1) (sr_tile_finish)"""
+    if nhwc:
+        planes, (H, W, cpp) = out.shape[0], out.shape[1:]
+    else:
+        planes, (H, W), cpp = out.shape[0] * out.shape[1], out.shape[2:], 1
+    a = [_p(t) for t in accs] + [None] * (3 - len(accs))
+    w = [_p(t) for t in wsums] + [None] * (3 - len(wsums))
+    LT.check(LT.lib().sr_tile_finish(a[0], a[1], a[2], w[0], w[1], w[2], _p(out), planes, H, W, cpp, len(accs), feather,
+                                   1 if process_output else 0, stream_ptr()))

@@ -43,24 +43,30 @@ class _Lowering:
     def attn(self, p, x, Cc, hh, ww):
         pb, W, B = self.pb, self.W, self.B
         HW = hh * ww
-        if HW % self.ke:
-            raise ValueError("VAE mid attention needs h*w to be a multiple of %d" % self.ke)
+        # the key dimension is the K of the second GEMM: padded to the K-step with zero keys (k rows beyond HW are zero, vt columns
+        # beyond HW are zero).  Their scores get a bias of -inf in the score GEMM's epilogue, so the row softmax over all HWp columns
+        # gives them exactly 0 and the valid columns what the unpadded softmax gives.  HW % ke == 0 emits exactly the unpadded plan.
+        HWp = _cdiv(HW, self.ke) * self.ke
+        mask = None
+        if HWp != HW:
+            mask = pb.buf(HWp, dtype=torch.float32, zero=True)
+            mask[HW:] = float("-inf")
         rows = _cdiv(HW, 128) * 128                 # K is the weight operand of the score GEMM: pad rows
         n = pb.buf(B, HW, Cc)
         pb.groupnorm(x, W[p + ".norm.g"], W[p + ".norm.beta"], n, B, HW, Cc, eps=1e-6, silu=False)
         q = pb.buf(B, HW, Cc)
         k = pb.buf(B, rows, Cc, zero=True)
-        vt = pb.buf(B, _cdiv(Cc, 128) * 128, HW, zero=True)
+        vt = pb.buf(B, _cdiv(Cc, 128) * 128, HWp, zero=True)
         pb.igemm(n, W[p + ".q"], q, B, hh, ww, Cc, Cc, bias=W[p + ".q.b"])
         for b in range(B):
             pb.igemm(n[b], W[p + ".k"], k[b], 1, hh, ww, Cc, Cc, bias=W[p + ".k.b"])
-            pb.igemm(n[b], W[p + ".v"], vt[b], 1, hh, ww, Cc, Cc, bias=W[p + ".v.b"], transpose_out=1, ldt=HW)
-        s = pb.buf(HW, HW)                          # one image at a time: 32 MiB of scores at 512^2 (fp16)
+            pb.igemm(n[b], W[p + ".v"], vt[b], 1, hh, ww, Cc, Cc, bias=W[p + ".v.b"], transpose_out=1, ldt=HWp)
+        s = pb.buf(HW, HWp)                         # one image at a time: 32 MiB of scores at 512^2 (fp16)
         o = pb.buf(B, HW, Cc)
         for b in range(B):
-            pb.igemm(q[b], k[b], s, HW, 1, 1, Cc, HW, scale=float(Cc) ** -0.5)
-            pb.softmax_rows(s, HW, HW)
-            pb.igemm(s, vt[b], o[b], HW, 1, 1, HW, Cc)
+            pb.igemm(q[b], k[b], s, HW, 1, 1, Cc, HWp, scale=float(Cc) ** -0.5, bias=mask)
+            pb.softmax_rows(s, HW, HWp)
+            pb.igemm(s, vt[b], o[b], HW, 1, 1, HWp, Cc)
         out = pb.buf(B, HW, Cc)
         pb.igemm(o, W[p + ".proj_out"], out, B, hh, ww, Cc, Cc, bias=W[p + ".proj_out.b"], residual=x)
         return out
