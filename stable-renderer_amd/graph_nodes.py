@@ -418,6 +418,114 @@ class VAEDecodeTiled:
         return (vae.decode_tiled(samples["samples"], tile_x=tile_size // 8, tile_y=tile_size // 8),)
 
 
+class EmptyLatentImage:
+    """comfyUI/nodes.py:1090-1106"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "generate"
+    CATEGORY = "latent"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"width": ("INT", {"default": 512, "min": 16, "max": 16384, "step": 8}),
+                             "height": ("INT", {"default": 512, "min": 16, "max": 16384, "step": 8}),
+                             "batch_size": ("INT", {"default": 1, "min": 1, "max": 4096})}}
+
+    def generate(self, width, height, batch_size=1):
+        return (N.LATENT(samples=torch.zeros([batch_size, 4, height // 8, width // 8], device="cuda")),)
+
+
+class LatentUpscale:
+    """comfyUI/nodes.py:1167-1199: pixel sizes, at least 64, // 8; a 0 keeps the aspect ratio, two 0s pass the latent through"""
+    upscale_methods = ["nearest-exact", "bilinear", "area", "bicubic", "bislerp"]
+    crop_methods = ["disabled", "center"]
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "upscale"
+    CATEGORY = "latent"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "upscale_method": (s.upscale_methods,),
+                             "width": ("INT", {"default": 512, "min": 0, "max": 16384, "step": 8}),
+                             "height": ("INT", {"default": 512, "min": 0, "max": 16384, "step": 8}), "crop": (s.crop_methods,)}}
+
+    def upscale(self, samples, upscale_method, width, height, crop):
+        from . import resample as RS
+        if upscale_method not in self.upscale_methods:
+            raise ValueError(f"LatentUpscale: upscale_method must be one of {self.upscale_methods}, got {upscale_method!r}")
+        size = RS.latent_upscale_size(samples["samples"].shape[2], samples["samples"].shape[3], width, height)
+        if size is None:
+            return (samples,)
+        s = samples.copy()                                       # the LATENT dict is copied, never mutated
+        s["samples"] = RS.common_upscale(samples["samples"], size[0], size[1], upscale_method, crop)
+        return (s,)
+
+
+class LatentUpscaleBy:
+    """comfyUI/nodes.py:1201-1218"""
+    upscale_methods = ["nearest-exact", "bilinear", "area", "bicubic", "bislerp"]
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "upscale"
+    CATEGORY = "latent"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "upscale_method": (s.upscale_methods,),
+                             "scale_by": ("FLOAT", {"default": 1.5, "min": 0.01, "max": 8.0, "step": 0.01})}}
+
+    def upscale(self, samples, upscale_method, scale_by):
+        from . import resample as RS
+        if upscale_method not in self.upscale_methods:
+            raise ValueError(f"LatentUpscaleBy: upscale_method must be one of {self.upscale_methods}, got {upscale_method!r}")
+        s = samples.copy()
+        width, height = RS.scale_by_size(samples["samples"].shape[2], samples["samples"].shape[3], scale_by)
+        s["samples"] = RS.common_upscale(samples["samples"], width, height, upscale_method, "disabled")
+        return (s,)
+
+
+class ImageScale:
+    """comfyUI/nodes.py:1731-1759: the IMAGE (N,H,W,C) is resampled where it lies, through its movedim(-1, 1) view"""
+    upscale_methods = ["nearest-exact", "bilinear", "area", "bicubic", "lanczos"]
+    crop_methods = ["disabled", "center"]
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "upscale"
+    CATEGORY = "image/upscaling"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "upscale_method": (s.upscale_methods,),
+                             "width": ("INT", {"default": 512, "min": 0, "max": 16384, "step": 1}),
+                             "height": ("INT", {"default": 512, "min": 0, "max": 16384, "step": 1}), "crop": (s.crop_methods,)}}
+
+    def upscale(self, image, upscale_method, width, height, crop):
+        from . import resample as RS
+        if upscale_method not in self.upscale_methods:
+            raise ValueError(f"ImageScale: upscale_method must be one of {self.upscale_methods}, got {upscale_method!r}")
+        size = RS.image_scale_size(image.shape[1], image.shape[2], width, height)
+        if size is None:
+            return (image,)
+        return (RS.common_upscale(image.movedim(-1, 1), size[0], size[1], upscale_method, crop).movedim(1, -1),)
+
+
+class ImageScaleBy:
+    """comfyUI/nodes.py:1761-1779"""
+    upscale_methods = ["nearest-exact", "bilinear", "area", "bicubic", "lanczos"]
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "upscale"
+    CATEGORY = "image/upscaling"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "upscale_method": (s.upscale_methods,),
+                             "scale_by": ("FLOAT", {"default": 1.0, "min": 0.01, "max": 8.0, "step": 0.01})}}
+
+    def upscale(self, image, upscale_method, scale_by):
+        from . import resample as RS
+        if upscale_method not in self.upscale_methods:
+            raise ValueError(f"ImageScaleBy: upscale_method must be one of {self.upscale_methods}, got {upscale_method!r}")
+        width, height = RS.scale_by_size(image.shape[1], image.shape[2], scale_by)
+        return (RS.common_upscale(image.movedim(-1, 1), width, height, upscale_method, "disabled").movedim(1, -1),)
+
+
 class LoadImage:
     """comfyUI/nodes.py:1623-1665 -> (IMAGE (1,H,W,3) in [0,1], MASK = 1 - alpha or 64x64 zeros).  ``image`` is a path, or a name
     under $SR_INPUT_DIR (the reference's input directory)"""
@@ -491,6 +599,8 @@ class IfValTypeEqual(N.StableRenderingNode):
 for _name, _cls in (("CheckpointLoaderSimple", CheckpointLoaderSimple), ("LoraLoaderModelOnly", LoraLoaderModelOnly),
                     ("ControlNetLoader", ControlNetLoader), ("ControlNetApply", ControlNetApply), ("ControlNetApplyAdvanced", ControlNetApplyAdvanced), ("CLIPTextEncode", CLIPTextEncode),
                     ("SceneTextEncode", SceneTextEncode), ("MaskedTextEncode", MaskedTextEncode), ("KSampler", KSampler), ("VAEDecode", VAEDecode), ("VAEEncode", VAEEncode), ("VAEDecodeTiled", VAEDecodeTiled), ("VAEEncodeTiled", VAEEncodeTiled), ("LoadImage", LoadImage),
+                    ("EmptyLatentImage", EmptyLatentImage), ("LatentUpscale", LatentUpscale), ("LatentUpscaleBy", LatentUpscaleBy),
+                    ("ImageScale", ImageScale), ("ImageScaleBy", ImageScaleBy),
                     ("IsNotNone", IsNotNone), ("If", If), ("IfValTypeEqual", IfValTypeEqual),
                     ("EngineData", N.EngineDataNode), ("VirtualEngineData", N.VirtualEngineDataNode),
                     ("InferenceOutput", N.InferenceOutputNode), ("EmptyCorrMaps", N.EmptyCorrMaps),

@@ -177,19 +177,35 @@ class Overlap:
 
 
 class ResizeOverlap(Overlap):
-    """latents are (conceptually) nearest-resized to the corr-map size, overlapped and resized back (overlap.py:180-222); the
-    kernel does all three at latent resolution."""
+    """latents are (conceptually) resized to the corr-map size, overlapped and resized back (overlap.py:155-222).  With the default
+    ``nearest`` the kernel does all three at latent resolution; ``bilinear``, ``bicubic``, ``area`` and ``nearest-exact`` resample up
+    (sr_resample), run the full-resolution overlap and resample down, composed as the reference composes them."""
     keep_nonzero = 1
+    interpolate_modes = ('nearest', 'bilinear', 'bicubic', 'area', 'nearest-exact')
 
     def __init__(self, alpha_scheduler, kernel_radius_scheduler, algorithm, verbose=True, interpolate_mode='nearest'):
         super().__init__(alpha_scheduler, kernel_radius_scheduler, algorithm, verbose)
-        if interpolate_mode != 'nearest':
-            raise NotImplementedError("only nearest interpolation is fused")
+        if interpolate_mode not in self.interpolate_modes:
+            raise ValueError(f"ResizeOverlap: interpolate_mode must be one of {self.interpolate_modes}, got {interpolate_mode!r}")
         self.interpolate_mode = interpolate_mode
+        self._full = Overlap(alpha_scheduler, kernel_radius_scheduler, algorithm, verbose)     # the (h, w) == (H, W) path of _run
 
     def __call__(self, frame_seq, corr_map, step=None, timestep=None, view_normal_map=None, **kwargs):
         alpha = self.alpha_scheduler(step, timestep)
         if alpha == 0:
             return frame_seq
-        out = self._run(torch.stack(list(frame_seq), 0), corr_map, alpha, int(self.kernel_radius_scheduler(step, timestep)), view_normal_map)
-        return [out[i] for i in range(out.shape[0])]
+        radius = int(self.kernel_radius_scheduler(step, timestep))
+        x = torch.stack(list(frame_seq), 0)
+        if self.interpolate_mode == 'nearest':
+            out = self._run(x, corr_map, alpha, radius, view_normal_map)
+            return [out[i] for i in range(out.shape[0])]
+        from . import resample as RS
+        T, B, Cc, h, w = x.shape
+        assert B == 1, "the legacy path handles one latent per frame"
+        H, W = corr_map.height, corr_map.width
+        xin = x.reshape(T, Cc, h, w).contiguous().float()
+        up = RS.resample(xin, H, W, self.interpolate_mode)                                     # overlap.py:208
+        ov = self._full._run(up.reshape(T, 1, Cc, H, W), corr_map, alpha, radius, view_normal_map)
+        down = RS.resample(ov.reshape(T, Cc, H, W), h, w, self.interpolate_mode)               # overlap.py:216
+        out = torch.where(down != 0, down, xin).reshape(T, 1, Cc, h, w)                        # overlap.py:221
+        return [out[i] for i in range(T)]
