@@ -174,7 +174,9 @@ typedef struct {
 } sr_attention_args;
 int sr_attention(const sr_attention_args* args, void* stream);
 
-/* small element-wise pieces of UNetModel.forward / BaseModel.apply_model */
+/* small element-wise pieces of UNetModel.forward / BaseModel.apply_model.
+ * Count contract of every element-wise and sampler entry point (this block and "Sampler arithmetic" below): a count of 0 (n, rows,
+ * B, ...) is SR_OK without a launch and leaves every buffer untouched; a negative count is SR_ERR_INVALID. */
 int sr_nchw_to_nhwc(const float* x, void* y, int32_t B, int32_t C, int32_t HW, int32_t Cpad, float scale_mul,
                     const float* per_batch_scale, int32_t dtype, void* stream);   /* y[b,p,c] = x[b,c,p]*s */
 int sr_nhwc_to_nchw(const void* x, float* y, int32_t B, int32_t C, int32_t HW, int32_t ldc, int32_t dtype,
@@ -286,7 +288,8 @@ int sr_cfg_combine(const float* x, const float* out_c, const float* cnt_c, const
 int sr_euler_step(float* x, const float* d, int64_t n, float dt, void* stream);           /* x += d*dt */
 /* VAE.encode's posterior sample (comfy/ldm/modules/distributions/distributions.py:24-37 via DiagonalGaussianRegularizer,
  * comfy/ldm/models/autoencoder.py:13-31): moments (B, HW, 2*zc) fp32 NHWC = [mean | logvar] from quant_conv;
- * z[b,c,p] = mean + exp(0.5*clamp(logvar,-30,20)) * noise[b,c,p]; noise / z (B, zc, HW) fp32 NCHW */
+ * z[b,c,p] = mean + exp(0.5*clamp(logvar,-30,20)) * noise[b,c,p]; noise / z (B, zc, HW) fp32 NCHW.  clamp as torch.clamp: a NaN
+ * log-variance stays NaN, so a non-finite moment gives a non-finite latent at its element (and nowhere else) */
 int sr_vae_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t zc, int32_t HW, void* stream);
 /* DDPMSampler_step + rescale; noise = host-drawn randn (may be NULL when sigma_next == 0) */
 int sr_ddpm_step(float* x, const float* denoised, const float* noise, int64_t n, float sigma, float sigma_next,

@@ -174,7 +174,9 @@ __global__ void vae_sample_kernel(const float* __restrict__ mom, const float* __
   if (i >= (int64_t)B * zc * HW) return;
   const int p = (int)(i % HW), c = (int)((i / HW) % zc), b = (int)(i / ((int64_t)HW * zc));
   const float* m = mom + ((int64_t)b * HW + p) * (2 * zc);
-  const float logvar = fminf(fmaxf(m[zc + c], -30.0f), 20.0f);
+  // torch.clamp semantics: a NaN log-variance stays NaN (fminf / fmaxf would return the finite bound)
+  const float lv = m[zc + c];
+  const float logvar = lv != lv ? lv : fminf(fmaxf(lv, -30.0f), 20.0f);
   z[i] = m[c] + expf(0.5f * logvar) * noise[i];
 }
 
@@ -210,12 +212,23 @@ __global__ void axpby_kernel(float* __restrict__ y, const float* __restrict__ x,
 
 inline dim3 g1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// Count contract of every entry point below: a negative count is SR_ERR_INVALID, a zero count is SR_OK without a launch (a
+// zero-block grid is an invalid launch configuration), and an element count whose 256-thread grid would not fit the x
+// dimension is SR_ERR_INVALID -- so nothing invalid is ever sent to the device.
+#define SR_COUNT_GUARD(name, neg, total)                                                        \
+  do {                                                                                          \
+    if (neg) SR_FAIL(SR_ERR_INVALID, name ": negative count");                                  \
+    if ((int64_t)(total) == 0) return SR_OK;                                                    \
+    if ((int64_t)(total) > (int64_t)0x7fffffff * 256) SR_FAIL(SR_ERR_INVALID, name ": count too large"); \
+  } while (0)
+
 }  // namespace
 
 extern "C" int sr_nchw_to_nhwc(const float* x, void* y, int32_t B, int32_t C, int32_t HW, int32_t Cpad, float scale_mul,
                                const float* pbs, int32_t dtype, void* stream) {
   if (!x || !y || Cpad < C) SR_FAIL(SR_ERR_INVALID, "sr_nchw_to_nhwc: bad args");
   const int64_t n = (int64_t)B * HW * Cpad;
+  SR_COUNT_GUARD("sr_nchw_to_nhwc", B < 0 || C < 0 || HW < 0, n);
   if (dtype == SR_F16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<_Float16>, g1(n), dim3(256), 0, sr_stream(stream), x, (_Float16*)y, B, C, HW, Cpad, scale_mul, pbs);
   else hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, g1(n), dim3(256), 0, sr_stream(stream), x, (float*)y, B, C, HW, Cpad, scale_mul, pbs);
   SR_CHECK_LAUNCH("sr_nchw_to_nhwc");
@@ -225,6 +238,7 @@ extern "C" int sr_nchw_to_nhwc(const float* x, void* y, int32_t B, int32_t C, in
 extern "C" int sr_nhwc_to_nchw(const void* x, float* y, int32_t B, int32_t C, int32_t HW, int32_t ldc, int32_t dtype, void* stream) {
   if (!x || !y || ldc < C) SR_FAIL(SR_ERR_INVALID, "sr_nhwc_to_nchw: bad args");
   const int64_t n = (int64_t)B * HW * C;
+  SR_COUNT_GUARD("sr_nhwc_to_nchw", B < 0 || C < 0 || HW < 0, n);
   if (dtype == SR_F16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<_Float16>, g1(n), dim3(256), 0, sr_stream(stream), (const _Float16*)x, y, B, C, HW, ldc);
   else hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, g1(n), dim3(256), 0, sr_stream(stream), (const float*)x, y, B, C, HW, ldc);
   SR_CHECK_LAUNCH("sr_nhwc_to_nchw");
@@ -233,6 +247,8 @@ extern "C" int sr_nhwc_to_nchw(const void* x, float* y, int32_t B, int32_t C, in
 
 extern "C" int sr_timestep_embedding(const float* t, void* y, int32_t B, int32_t dim, int32_t dtype, void* stream) {
   if (!t || !y || dim % 2) SR_FAIL(SR_ERR_INVALID, "sr_timestep_embedding: bad args");
+  SR_COUNT_GUARD("sr_timestep_embedding", B < 0 || dim < 0, (int64_t)B * dim);
+  if ((int64_t)B * dim > 0x7fffffff) SR_FAIL(SR_ERR_INVALID, "sr_timestep_embedding: B * dim too large");
   if (dtype == SR_F16) hipLaunchKernelGGL(temb_kernel<_Float16>, g1((int64_t)B * dim), dim3(256), 0, sr_stream(stream), t, (_Float16*)y, B, dim);
   else hipLaunchKernelGGL(temb_kernel<float>, g1((int64_t)B * dim), dim3(256), 0, sr_stream(stream), t, (float*)y, B, dim);
   SR_CHECK_LAUNCH("sr_timestep_embedding");
@@ -241,6 +257,7 @@ extern "C" int sr_timestep_embedding(const float* t, void* y, int32_t B, int32_t
 
 extern "C" int sr_silu(const void* x, void* y, int64_t n, int32_t dtype, void* stream) {
   if (!x || !y) SR_FAIL(SR_ERR_INVALID, "sr_silu: null");
+  SR_COUNT_GUARD("sr_silu", n < 0, n);
   if (dtype == SR_F16) hipLaunchKernelGGL(silu_kernel<_Float16>, g1(n), dim3(256), 0, sr_stream(stream), (const _Float16*)x, (_Float16*)y, n);
   else hipLaunchKernelGGL(silu_kernel<float>, g1(n), dim3(256), 0, sr_stream(stream), (const float*)x, (float*)y, n);
   SR_CHECK_LAUNCH("sr_silu");
@@ -268,6 +285,8 @@ extern "C" int sr_cache_touch(const void* p, int64_t bytes, void* stream) {
 
 extern "C" int sr_cast(const void* x, int32_t sd, void* y, int32_t dd, int64_t n, void* stream) {
   if (!x || !y) SR_FAIL(SR_ERR_INVALID, "sr_cast: null");
+  if ((sd != SR_F16 && sd != SR_F32) || (dd != SR_F16 && dd != SR_F32)) SR_FAIL(SR_ERR_INVALID, "sr_cast: unknown dtype");
+  SR_COUNT_GUARD("sr_cast", n < 0, n);
   hipStream_t st = sr_stream(stream);
   if (sd == SR_F32 && dd == SR_F16) hipLaunchKernelGGL((cast_kernel<float, _Float16>), g1(n), dim3(256), 0, st, (const float*)x, (_Float16*)y, n);
   else if (sd == SR_F16 && dd == SR_F32) hipLaunchKernelGGL((cast_kernel<_Float16, float>), g1(n), dim3(256), 0, st, (const _Float16*)x, (float*)y, n);
@@ -279,6 +298,8 @@ extern "C" int sr_cast(const void* x, int32_t sd, void* y, int32_t dd, int64_t n
 
 extern "C" int sr_softmax_rows(void* x, int32_t rows, int32_t cols, int32_t dtype, void* stream) {
   if (!x) SR_FAIL(SR_ERR_INVALID, "sr_softmax_rows: null");
+  if (rows < 0 || cols < 0) SR_FAIL(SR_ERR_INVALID, "sr_softmax_rows: negative count");
+  if (rows == 0 || cols == 0) return SR_OK;
   if (dtype == SR_F16) hipLaunchKernelGGL(softmax_rows_kernel<_Float16>, dim3(rows), dim3(256), 0, sr_stream(stream), (_Float16*)x, cols);
   else hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(rows), dim3(256), 0, sr_stream(stream), (float*)x, cols);
   SR_CHECK_LAUNCH("sr_softmax_rows");
@@ -287,6 +308,7 @@ extern "C" int sr_softmax_rows(void* x, int32_t rows, int32_t cols, int32_t dtyp
 
 extern "C" int sr_add_scaled(const void* a, const void* b, void* y, int64_t n, float s, int32_t dtype, void* stream) {
   if (!a || !b || !y) SR_FAIL(SR_ERR_INVALID, "sr_add_scaled: null");
+  SR_COUNT_GUARD("sr_add_scaled", n < 0, n);
   if (dtype == SR_F16) hipLaunchKernelGGL(add_scaled_kernel<_Float16>, g1(n), dim3(256), 0, sr_stream(stream), (const _Float16*)a, (const _Float16*)b, (_Float16*)y, n, s);
   else hipLaunchKernelGGL(add_scaled_kernel<float>, g1(n), dim3(256), 0, sr_stream(stream), (const float*)a, (const float*)b, (float*)y, n, s);
   SR_CHECK_LAUNCH("sr_add_scaled");
@@ -298,6 +320,7 @@ extern "C" int sr_gather_rows(const void* x, const int32_t* sel, void* y, int32_
   if (!x || !sel || !y || row_bytes <= 0 || row_bytes % 16 || nsel < 0 || n_rows < 1) SR_FAIL(SR_ERR_INVALID, "sr_gather_rows: bad args");
   if (nsel == 0) return SR_OK;
   const int64_t rc = row_bytes / 16;
+  if (rc > ((int64_t)0x7fffffff * 256) / nsel) SR_FAIL(SR_ERR_INVALID, "sr_gather_rows: count too large");
   hipLaunchKernelGGL(gather_rows_kernel, g1((int64_t)nsel * rc), dim3(256), 0, sr_stream(stream), (const uint4*)x, sel, (uint4*)y, nsel, n_rows, rc,
                      err_flag);
   SR_CHECK_LAUNCH("sr_gather_rows");
@@ -306,6 +329,7 @@ extern "C" int sr_gather_rows(const void* x, const int32_t* sel, void* y, int32_
 
 extern "C" int sr_eps_scale_input(const float* x, float* xin, int64_t n, int32_t copies, float sigma, void* stream) {
   if (!x || !xin || (copies != 1 && copies != 2)) SR_FAIL(SR_ERR_INVALID, "sr_eps_scale_input: bad args");
+  SR_COUNT_GUARD("sr_eps_scale_input", n < 0, n);
   const float inv = 1.0f / sqrtf(sigma * sigma + 1.0f);     // x / (sigma^2 + 1)^0.5
   hipLaunchKernelGGL(eps_scale_kernel, g1(n), dim3(256), 0, sr_stream(stream), x, xin, n, copies, inv);
   SR_CHECK_LAUNCH("sr_eps_scale_input");
@@ -315,6 +339,7 @@ extern "C" int sr_eps_scale_input(const float* x, float* xin, int64_t n, int32_t
 extern "C" int sr_cfg_denoise(const float* x, const float* eps, float* den, float* d, int64_t n, int32_t copies, float sigma,
                               float cfg, void* stream) {
   if (!x || !eps || !den || (copies != 1 && copies != 2)) SR_FAIL(SR_ERR_INVALID, "sr_cfg_denoise: bad args");
+  SR_COUNT_GUARD("sr_cfg_denoise", n < 0, n);
   hipLaunchKernelGGL(cfg_denoise_kernel, g1(n), dim3(256), 0, sr_stream(stream), x, eps, den, d, n, copies, sigma, cfg);
   SR_CHECK_LAUNCH("sr_cfg_denoise");
   return SR_OK;
@@ -324,6 +349,7 @@ extern "C" int sr_cond_crop_scale(const float* x, float* xin, int32_t N, int32_t
                                   int32_t x0, int32_t chunks, float sigma, void* stream) {
   if (!x || !xin || chunks < 1 || ah < 1 || aw < 1 || y0 < 0 || x0 < 0 || y0 + ah > h || x0 + aw > w)
     SR_FAIL(SR_ERR_INVALID, "sr_cond_crop_scale: bad args (area outside the latent?)");
+  SR_COUNT_GUARD("sr_cond_crop_scale", N < 0 || C < 0, (int64_t)N * C * ah * aw);
   const float inv = 1.0f / sqrtf(sigma * sigma + 1.0f);
   hipLaunchKernelGGL(cond_crop_scale_kernel, g1((int64_t)N * C * ah * aw), dim3(256), 0, sr_stream(stream), x, xin, N, C, h, w, ah, aw, y0, x0,
                      chunks, inv);
@@ -337,6 +363,7 @@ extern "C" int sr_cond_accumulate(const float* x, const float* eps, const float*
   if (!x || !eps || !mult || !kinds || !out_c || !cnt_c || !out_u || !cnt_u || chunks < 1 || ah < 1 || aw < 1 || y0 < 0 || x0 < 0 ||
       y0 + ah > h || x0 + aw > w)
     SR_FAIL(SR_ERR_INVALID, "sr_cond_accumulate: bad args (area outside the latent?)");
+  SR_COUNT_GUARD("sr_cond_accumulate", N < 0 || C < 0, (int64_t)N * C * ah * aw);
   hipLaunchKernelGGL(cond_accumulate_kernel, g1((int64_t)N * C * ah * aw), dim3(256), 0, sr_stream(stream), x, eps, mult, kinds, out_c, cnt_c,
                      out_u, cnt_u, N, C, h, w, ah, aw, y0, x0, chunks, sigma);
   SR_CHECK_LAUNCH("sr_cond_accumulate");
@@ -346,13 +373,15 @@ extern "C" int sr_cond_accumulate(const float* x, const float* eps, const float*
 extern "C" int sr_cfg_combine(const float* x, const float* out_c, const float* cnt_c, const float* out_u, const float* cnt_u,
                               float* denoised, float* d, int64_t n, float sigma, float cfg, void* stream) {
   if (!x || !out_c || !cnt_c || !out_u || !cnt_u || !denoised) SR_FAIL(SR_ERR_INVALID, "sr_cfg_combine: null");
+  SR_COUNT_GUARD("sr_cfg_combine", n < 0, n);
   hipLaunchKernelGGL(cfg_combine_kernel, g1(n), dim3(256), 0, sr_stream(stream), x, out_c, cnt_c, out_u, cnt_u, denoised, d, n, sigma, cfg);
   SR_CHECK_LAUNCH("sr_cfg_combine");
   return SR_OK;
 }
 
 extern "C" int sr_vae_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t zc, int32_t HW, void* stream) {
-  if (!moments || !noise || !z || B < 1 || zc < 1 || HW < 1) SR_FAIL(SR_ERR_INVALID, "sr_vae_sample: bad args");
+  if (!moments || !noise || !z) SR_FAIL(SR_ERR_INVALID, "sr_vae_sample: null");
+  SR_COUNT_GUARD("sr_vae_sample", B < 0 || zc < 0 || HW < 0, (int64_t)B * zc * HW);
   hipLaunchKernelGGL(vae_sample_kernel, g1((int64_t)B * zc * HW), dim3(256), 0, sr_stream(stream), moments, noise, z, B, zc, HW);
   SR_CHECK_LAUNCH("sr_vae_sample");
   return SR_OK;
@@ -360,6 +389,7 @@ extern "C" int sr_vae_sample(const float* moments, const float* noise, float* z,
 
 extern "C" int sr_euler_step(float* x, const float* d, int64_t n, float dt, void* stream) {
   if (!x || !d) SR_FAIL(SR_ERR_INVALID, "sr_euler_step: null");
+  SR_COUNT_GUARD("sr_euler_step", n < 0, n);
   hipLaunchKernelGGL(euler_kernel, g1(n), dim3(256), 0, sr_stream(stream), x, d, n, dt);
   SR_CHECK_LAUNCH("sr_euler_step");
   return SR_OK;
@@ -367,6 +397,7 @@ extern "C" int sr_euler_step(float* x, const float* d, int64_t n, float dt, void
 
 extern "C" int sr_ddpm_step(float* x, const float* den, const float* noise, int64_t n, float sigma, float sigma_next, void* stream) {
   if (!x || !den) SR_FAIL(SR_ERR_INVALID, "sr_ddpm_step: null");
+  SR_COUNT_GUARD("sr_ddpm_step", n < 0, n);
   // scalar algebra of DDPMSampler_step in fp32, as torch does on 0-d fp32 tensors
   const float in_scale = 1.0f / sqrtf(1.0f + sigma * sigma);
   const float ac = 1.0f / (sigma * sigma + 1.0f), acp = 1.0f / (sigma_next * sigma_next + 1.0f);
@@ -388,6 +419,7 @@ extern "C" int sr_ddpm_step(float* x, const float* den, const float* noise, int6
 
 extern "C" int sr_lcm_step(float* x, const float* den, const float* noise, int64_t n, float sigma_next, void* stream) {
   if (!x || !den) SR_FAIL(SR_ERR_INVALID, "sr_lcm_step: null");
+  SR_COUNT_GUARD("sr_lcm_step", n < 0, n);
   const float* nz = sigma_next > 0.f ? noise : nullptr;
   if (sigma_next > 0.f && !noise) SR_FAIL(SR_ERR_INVALID, "sr_lcm_step: noise required");
   hipLaunchKernelGGL(lcm_kernel, g1(n), dim3(256), 0, sr_stream(stream), x, den, nz, n, sigma_next);
@@ -397,6 +429,7 @@ extern "C" int sr_lcm_step(float* x, const float* den, const float* noise, int64
 
 extern "C" int sr_axpby(float* y, const float* x, int64_t n, float a, float b, void* stream) {
   if (!x || !y) SR_FAIL(SR_ERR_INVALID, "sr_axpby: null");
+  SR_COUNT_GUARD("sr_axpby", n < 0, n);
   hipLaunchKernelGGL(axpby_kernel, g1(n), dim3(256), 0, sr_stream(stream), y, x, n, a, b);
   SR_CHECK_LAUNCH("sr_axpby");
   return SR_OK;
