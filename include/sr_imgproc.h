@@ -1,0 +1,79 @@
+/* C ABI of libsr_imgproc.so (stable-renderer_amd/csrc/imgproc/): the image and mask filters of ComfyUI's
+ * comfy_extras/nodes_post_processing.py (Blur, Sharpen, Blend) and comfy_extras/nodes_mask.py (composite(), GrowMask, FeatherMask,
+ * MaskComposite, ImageColorToMask).  Same conventions as include/sr_hip.h, sr_tiled.h and sr_resample.h: caller-owned device
+ * pointers to fp32, `stream` a hipStream_t, no allocation, no atomics and no synchronisation inside (every entry point can be captured
+ * into a graph), 0 on success or a negative code with the text in sr_imgproc_last_error() (thread-local).  Strides are HOST arrays
+ * of element strides.  A destination never aliases a source. */
+#ifndef SR_IMGPROC_H
+#define SR_IMGPROC_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum { SR_IMGPROC_OK = 0, SR_IMGPROC_ERR_INVALID = -1, SR_IMGPROC_ERR_LAUNCH = -2 };
+/* Blend.blend_mode (nodes_post_processing.py:47-61) */
+enum { SR_BLEND_NORMAL = 0, SR_BLEND_MULTIPLY = 1, SR_BLEND_SCREEN = 2, SR_BLEND_OVERLAY = 3, SR_BLEND_SOFT_LIGHT = 4, SR_BLEND_DIFFERENCE = 5 };
+/* MaskComposite.combine's operation (nodes_mask.py:247-258) */
+enum { SR_COMBINE_MULTIPLY = 0, SR_COMBINE_ADD = 1, SR_COMBINE_SUBTRACT = 2, SR_COMBINE_AND = 3, SR_COMBINE_OR = 4, SR_COMBINE_XOR = 5 };
+enum { SR_GAUSS_MAX_RADIUS = 31, SR_GROW_MAX_STEP = 16 };
+
+const char* sr_imgproc_last_error(void);
+const char* sr_imgproc_source_hash(void);                   /* hash of the sources this image was built from */
+
+/* Blur.blur and Sharpen.sharpen (nodes_post_processing.py:66-115, :223-242): the depthwise (2r+1)^2 Gaussian over an IMAGE
+ * (B,H,W,C), C = 1..4, 1 <= r <= 31, r < H, r < W, as a reflect-padded valid convolution.  The weights are
+ *   g(i, j) = w(i) w(j),  w(k) = e(k) / sum e,  e(k) = exp(-t_k^2 / (2 sigma^2)),  t = linspace(-1, 1, 2r+1)
+ * (coordinates normalised to [-1, 1], not pixels), formed in double on the host.  One launch: the tile and its halo go to LDS, the
+ * horizontal pass writes LDS in double, the vertical pass sums in double and writes dst once.
+ *   amount == 0:  dst = blur(src)
+ *   amount  > 0:  dst = clamp((1 + amount) src - amount blur(src), 0, 1)      amount = 10 alpha: the reference's kernel
+ *                 -(10 alpha) g with the centre raised so that it sums to 1
+ * src_strides: (b, y, x, c); dst is contiguous (B,H,W,C). */
+int sr_filter_gauss(const float* src, float* dst, int32_t B, int32_t H, int32_t W, int32_t C, const int64_t* src_strides,
+                    int32_t radius, double sigma, double amount, void* stream);
+
+/* GrowMask.expand_mask (nodes_mask.py:326-342): |expand| iterations of the 3x3 grey dilation (expand > 0) or erosion (expand < 0)
+ * with the cross footprint (tapered != 0) or the full one, pixels outside the mask ignored: up to SR_GROW_MAX_STEP iterations per
+ * launch, on a tile and its halo in LDS.  src (N,H,W) with strides (n, y, x); dst contiguous.  tmp: contiguous (N,H,W), needed when
+ * min(|expand|, H + W) > SR_GROW_MAX_STEP (may be NULL otherwise).  expand == 0 copies. */
+int sr_mask_grow(const float* src, float* dst, float* tmp, int32_t N, int32_t H, int32_t W, const int64_t* src_strides,
+                 int32_t expand, int32_t tapered, void* stream);
+
+/* FeatherMask.feather (nodes_mask.py:283-307): dst = ((((src * l) * r) * t) * b) in fp32, each rate the double (k + 1) / n rounded
+ * to fp32 (1 where the loop does not touch the pixel).  Widths are clamped to the mask.  The reference's right and bottom loops
+ * index -k: k = 0 is column (row) 0 with rate 1/n, k >= 1 is column W - k with rate (k + 1) / n.  src strides (n, y, x). */
+int sr_mask_feather(const float* src, float* dst, int32_t N, int32_t H, int32_t W, const int64_t* src_strides, int32_t left,
+                    int32_t top, int32_t right, int32_t bottom, void* stream);
+
+/* composite() (nodes_mask.py:8-40) on a destination that the caller has cloned: for b < B, c < C, y < h, x < w
+ *   dst[b, c, top + y, left + x] = m src[b % Bs, c, y, x] + (1 - m) dst[...],  m = mask ? mask[b % Bm, y, x] : 1
+ * evaluated in double and rounded once; with no mask it is a copy.  (h, w) is the visible region the caller derived
+ * (nodes_mask.py:15-33); h == 0 or w == 0 is a no-op.  dst_strides / src_strides: (b, c, y, x), so an IMAGE is composited in its
+ * NHWC memory and a latent in NCHW; mask (Bm, >= h, >= w) with strides (b, y, x). */
+int sr_composite(float* dst, const float* src, const float* mask, int32_t B, int32_t C, int32_t Hd, int32_t Wd, int32_t Bs,
+                 int32_t Bm, int32_t top, int32_t left, int32_t h, int32_t w, const int64_t* dst_strides, const int64_t* src_strides,
+                 const int64_t* mask_strides, void* stream);
+
+/* Blend.blend_images (nodes_post_processing.py:35-64): dst = clamp(a (1 - f) + mode(a, b) f, 0, 1) over n elements, evaluated in
+ * double and rounded once.  a and b are (B,H,W,C) with strides (b, y, x, c); dst is contiguous. */
+int sr_blend(const float* a, const float* b, float* dst, int32_t B, int32_t H, int32_t W, int32_t C, const int64_t* a_strides,
+             const int64_t* b_strides, double factor, int32_t mode, void* stream);
+
+/* MaskComposite.combine (nodes_mask.py:236-262): dst = clamp(d, 0, 1) outside the window, clamp(op(d, s), 0, 1) inside, the window
+ * being rows [y, min(y + Hs, H)) and columns [x, min(x + Ws, W)) of the destination and the top-left corner of the source.  The
+ * arithmetic operations are single fp32 operations; and / or / xor act on rint(v) != 0 (round half to even).  dest (N,H,W) strides
+ * (n, y, x); source (Ns,Hs,Ws), Ns == N or 1; dst contiguous. */
+int sr_mask_combine(const float* dest, const float* source, float* dst, int32_t N, int32_t H, int32_t W, int32_t Ns, int32_t Hs,
+                    int32_t Ws, const int64_t* dest_strides, const int64_t* source_strides, int32_t x, int32_t y, int32_t op,
+                    void* stream);
+
+/* ImageColorToMask.image_to_mask (nodes_mask.py:147-151): dst = 255.0 where (R << 16) + (G << 8) + B == color, 0 elsewhere, with
+ * R, G, B = rint(clamp(v, 0, 1) * 255.f) of channels 0..2.  image (B,H,W,C >= 3) strides (b, y, x, c); dst contiguous (B,H,W). */
+int sr_color_to_mask(const float* image, float* dst, int32_t B, int32_t H, int32_t W, const int64_t* image_strides, int32_t color,
+                     void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

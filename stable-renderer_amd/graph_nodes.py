@@ -526,6 +526,291 @@ class ImageScaleBy:
         return (RS.common_upscale(image.movedim(-1, 1), width, height, upscale_method, "disabled").movedim(1, -1),)
 
 
+# ---- image and mask filters (comfy_extras/nodes_post_processing.py, comfy_extras/nodes_mask.py) over imgproc.py ------------------------
+MAX_RESOLUTION = 8192
+
+
+def _int(default, lo, hi, step=1):
+    return ("INT", {"default": default, "min": lo, "max": hi, "step": step})
+
+
+def _dev(t):
+    """what LoadImage read on the host goes to the device here: imgproc.py takes device tensors only"""
+    return t if t is None or t.is_cuda else t.to(device="cuda", dtype=torch.float32)
+
+
+class ImageBlur:
+    """nodes_post_processing.py:72-115"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "blur"
+    CATEGORY = "image/postprocessing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "blur_radius": _int(1, 1, 31),
+                             "sigma": ("FLOAT", {"default": 1.0, "min": 0.1, "max": 10.0, "step": 0.1})}}
+
+    def blur(self, image, blur_radius, sigma):
+        from . import imgproc as IP
+        return (IP.blur(_dev(image), blur_radius, sigma),)
+
+
+class ImageSharpen:
+    """nodes_post_processing.py:188-242"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "sharpen"
+    CATEGORY = "image/postprocessing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "sharpen_radius": _int(1, 1, 31),
+                             "sigma": ("FLOAT", {"default": 1.0, "min": 0.1, "max": 10.0, "step": 0.1}),
+                             "alpha": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 5.0, "step": 0.1})}}
+
+    def sharpen(self, image, sharpen_radius, sigma, alpha):
+        from . import imgproc as IP
+        return (IP.sharpen(_dev(image), sharpen_radius, sigma, alpha),)
+
+
+class ImageBlend:
+    """nodes_post_processing.py:10-64"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "blend_images"
+    CATEGORY = "image/postprocessing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image1": ("IMAGE",), "image2": ("IMAGE",),
+                             "blend_factor": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "blend_mode": (["normal", "multiply", "screen", "overlay", "soft_light", "difference"],)}}
+
+    def blend_images(self, image1, image2, blend_factor, blend_mode):
+        from . import imgproc as IP
+        return (IP.blend(_dev(image1), _dev(image2), blend_factor, blend_mode),)
+
+
+class ImageScaleToTotalPixels:
+    """nodes_post_processing.py:244-268"""
+    upscale_methods = ["nearest-exact", "bilinear", "area", "bicubic", "lanczos"]
+    crop_methods = ["disabled", "center"]
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "upscale"
+    CATEGORY = "image/upscaling"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "upscale_method": (s.upscale_methods,),
+                             "megapixels": ("FLOAT", {"default": 1.0, "min": 0.01, "max": 16.0, "step": 0.01})}}
+
+    def upscale(self, image, upscale_method, megapixels):
+        import math
+        from . import resample as RS
+        if upscale_method not in self.upscale_methods:
+            raise ValueError(f"ImageScaleToTotalPixels: upscale_method must be one of {self.upscale_methods}, got {upscale_method!r}")
+        samples = image.movedim(-1, 1)
+        total = int(megapixels * 1024 * 1024)
+        scale_by = math.sqrt(total / (samples.shape[3] * samples.shape[2]))
+        width, height = round(samples.shape[3] * scale_by), round(samples.shape[2] * scale_by)
+        return (RS.common_upscale(samples, width, height, upscale_method, "disabled").movedim(1, -1),)
+
+
+class LatentCompositeMasked:
+    """nodes_mask.py:42-67: x and y in pixels, // 8 into the latent"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "composite"
+    CATEGORY = "latent"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"destination": ("LATENT",), "source": ("LATENT",), "x": _int(0, 0, MAX_RESOLUTION, 8),
+                             "y": _int(0, 0, MAX_RESOLUTION, 8), "resize_source": ("BOOLEAN", {"default": False})},
+                "optional": {"mask": ("MASK",)}}
+
+    def composite(self, destination, source, x, y, resize_source, mask=None):
+        from . import imgproc as IP
+        output = destination.copy()                              # the LATENT dict is copied, never mutated
+        output["samples"] = IP.composite(_dev(destination["samples"]), _dev(source["samples"]), x, y, _dev(mask), 8, resize_source)
+        return (output,)
+
+
+class ImageCompositeMasked:
+    """nodes_mask.py:69-92: the IMAGE is composited in its (N,H,W,C) memory, through its movedim(-1, 1) view"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "composite"
+    CATEGORY = "image"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"destination": ("IMAGE",), "source": ("IMAGE",), "x": _int(0, 0, MAX_RESOLUTION),
+                             "y": _int(0, 0, MAX_RESOLUTION), "resize_source": ("BOOLEAN", {"default": False})},
+                "optional": {"mask": ("MASK",)}}
+
+    def composite(self, destination, source, x, y, resize_source, mask=None):
+        from . import imgproc as IP
+        return (IP.composite(_dev(destination).movedim(-1, 1), _dev(source).movedim(-1, 1), x, y, _dev(mask), 1, resize_source).movedim(1, -1),)
+
+
+class MaskToImage:
+    """nodes_mask.py:94-110: a view"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "mask_to_image"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"mask": ("MASK",)}}
+
+    def mask_to_image(self, mask):
+        return (mask.reshape((-1, 1, mask.shape[-2], mask.shape[-1])).movedim(1, -1).expand(-1, -1, -1, 3),)
+
+
+class ImageToMask:
+    """nodes_mask.py:112-130: a view"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "image_to_mask"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "channel": (["red", "green", "blue", "alpha"],)}}
+
+    def image_to_mask(self, image, channel):
+        channels = ["red", "green", "blue", "alpha"]
+        if channel not in channels:
+            raise ValueError(f"ImageToMask: channel must be one of {channels}, got {channel!r}")
+        return (image[:, :, :, channels.index(channel)],)
+
+
+class ImageColorToMask:
+    """nodes_mask.py:132-151"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "image_to_mask"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",),
+                             "color": ("INT", {"default": 0, "min": 0, "max": 0xFFFFFF, "step": 1, "display": "color"})}}
+
+    def image_to_mask(self, image, color):
+        from . import imgproc as IP
+        return (IP.color_to_mask(_dev(image), color),)
+
+
+class SolidMask:
+    """nodes_mask.py:153-172, made on the device"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "solid"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"value": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "width": _int(512, 1, MAX_RESOLUTION), "height": _int(512, 1, MAX_RESOLUTION)}}
+
+    def solid(self, value, width, height):
+        return (torch.full((1, height, width), value, dtype=torch.float32, device="cuda"),)
+
+
+class InvertMask:
+    """nodes_mask.py:174-191"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "invert"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"mask": ("MASK",)}}
+
+    def invert(self, mask):
+        return (1.0 - mask,)
+
+
+class CropMask:
+    """nodes_mask.py:193-215: a view"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "crop"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"mask": ("MASK",), "x": _int(0, 0, MAX_RESOLUTION), "y": _int(0, 0, MAX_RESOLUTION),
+                             "width": _int(512, 1, MAX_RESOLUTION), "height": _int(512, 1, MAX_RESOLUTION)}}
+
+    def crop(self, mask, x, y, width, height):
+        mask = mask.reshape((-1, mask.shape[-2], mask.shape[-1]))
+        return (mask[:, y:y + height, x:x + width],)
+
+
+class MaskComposite:
+    """nodes_mask.py:217-262"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "combine"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"destination": ("MASK",), "source": ("MASK",), "x": _int(0, 0, MAX_RESOLUTION), "y": _int(0, 0, MAX_RESOLUTION),
+                             "operation": (["multiply", "add", "subtract", "and", "or", "xor"],)}}
+
+    def combine(self, destination, source, x, y, operation):
+        from . import imgproc as IP
+        return (IP.mask_composite(_dev(destination), _dev(source), x, y, operation),)
+
+
+class FeatherMask:
+    """nodes_mask.py:264-307"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "feather"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"mask": ("MASK",), "left": _int(0, 0, MAX_RESOLUTION), "top": _int(0, 0, MAX_RESOLUTION),
+                             "right": _int(0, 0, MAX_RESOLUTION), "bottom": _int(0, 0, MAX_RESOLUTION)}}
+
+    def feather(self, mask, left, top, right, bottom):
+        from . import imgproc as IP
+        return (IP.feather_mask(_dev(mask), left, top, right, bottom),)
+
+
+class GrowMask:
+    """nodes_mask.py:309-342"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "expand_mask"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"mask": ("MASK",), "expand": _int(0, -MAX_RESOLUTION, MAX_RESOLUTION),
+                             "tapered_corners": ("BOOLEAN", {"default": True})}}
+
+    def expand_mask(self, mask, expand, tapered_corners):
+        from . import imgproc as IP
+        return (IP.grow_mask(_dev(mask), expand, tapered_corners),)
+
+
+class ThresholdMask:
+    """nodes_mask.py:344-361"""
+    RETURN_TYPES = ("MASK",)
+    FUNCTION = "image_to_mask"
+    CATEGORY = "mask"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"mask": ("MASK",), "value": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 1.0, "step": 0.01})}}
+
+    def image_to_mask(self, mask, value):
+        return ((mask > value).float(),)
+
+
+IMGPROC_NODES = {"ImageBlur": ImageBlur, "ImageSharpen": ImageSharpen, "ImageBlend": ImageBlend, "ImageScaleToTotalPixels": ImageScaleToTotalPixels,
+                 "LatentCompositeMasked": LatentCompositeMasked, "ImageCompositeMasked": ImageCompositeMasked, "MaskToImage": MaskToImage,
+                 "ImageToMask": ImageToMask, "ImageColorToMask": ImageColorToMask, "SolidMask": SolidMask, "InvertMask": InvertMask,
+                 "CropMask": CropMask, "MaskComposite": MaskComposite, "FeatherMask": FeatherMask, "GrowMask": GrowMask,
+                 "ThresholdMask": ThresholdMask}
+
+
 class LoadImage:
     """comfyUI/nodes.py:1623-1665 -> (IMAGE (1,H,W,3) in [0,1], MASK = 1 - alpha or 64x64 zeros).  ``image`` is a path, or a name
     under $SR_INPUT_DIR (the reference's input directory)"""
@@ -612,6 +897,9 @@ for _name, _cls in (("CheckpointLoaderSimple", CheckpointLoaderSimple), ("LoraLo
 from . import extra_nodes as _X  # noqa: E402
 
 for _name, _cls in _X.ALL.items():
+    register_node(_name, _cls)
+
+for _name, _cls in IMGPROC_NODES.items():
     register_node(_name, _cls)
 
 
