@@ -1,4 +1,4 @@
-/* C ABI of libsr_imgproc.so (stable-renderer_amd/csrc/imgproc/): the image and mask filters of ComfyUI's
+/* C ABI of libsr_imgproc.so (stable-renderer_amd/csrc/imgproc/, built by csrc/sidelib.py): the image and mask filters of ComfyUI's
  * comfy_extras/nodes_post_processing.py (Blur, Sharpen, Blend) and comfy_extras/nodes_mask.py (composite(), GrowMask, FeatherMask,
  * MaskComposite, ImageColorToMask).  Same conventions as include/sr_hip.h, sr_tiled.h and sr_resample.h: caller-owned device
  * pointers to fp32, `stream` a hipStream_t, no allocation, no atomics and no synchronisation inside (every entry point can be captured

@@ -1,4 +1,4 @@
-/* C ABI of libsr_resample.so (stable-renderer_amd/csrc/resample/): comfy.utils.common_upscale (comfyUI/comfy/utils.py:418-443) --
+/* C ABI of libsr_resample.so (stable-renderer_amd/csrc/resample/, built by csrc/sidelib.py): comfy.utils.common_upscale (comfyUI/comfy/utils.py:418-443) --
  * torch.nn.functional.interpolate in five modes, bislerp (utils.py:335-409) and the 8-bit Lanczos of utils.py:411-416.  Same conventions
  * as include/sr_hip.h and include/sr_tiled.h: caller-owned device pointers, `stream` a hipStream_t, no allocation, no atomics and no
  * synchronisation inside (every entry point can be captured into a graph), 0 on success or a negative code with the text in

@@ -1,4 +1,4 @@
-/* C ABI of libsr_tiled.so (stable-renderer_amd/csrc/tiled/): the tiled VAE of comfyUI/comfy/sd.py:302-327
+/* C ABI of libsr_tiled.so (stable-renderer_amd/csrc/tiled/, built by csrc/sidelib.py): the tiled VAE of comfyUI/comfy/sd.py:302-327
  * (VAE.decode_tiled_ / VAE.encode_tiled_) = three passes of comfy.utils.tiled_scale (comfyUI/comfy/utils.py:448-475), averaged.
  * Helpers around the per-tile VAE launch plans of libsr_hip.so (include/sr_hip.h); same conventions: caller-owned device
  * pointers, `stream` a hipStream_t, no allocation or synchronisation inside, 0 on success or a negative code with the text in

@@ -3,6 +3,9 @@ the shared library is missing or a symbol is absent, import of the compute modul
 import ctypes as C
 import os
 
+from . import _native
+from ._native import SrHipError  # noqa: F401  (raised by every loader; its users import it from here)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsr_hip.so")
 _DEV_LIB = os.environ.get("SR_DEV_LIB")          # development only: an experimental build of the library (tools/); no hash check
@@ -156,90 +159,21 @@ SYMBOLS = {
 _lib = None
 
 
-class SrHipError(RuntimeError):
-    pass
-
-
 def _build_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("sr_build", os.path.join(_HERE, "csrc", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _load():
-    L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(L, name)          # AttributeError if the symbol is missing: loud by design
-        fn.restype = res
-        fn.argtypes = args
-    return L
+    return _native.load_module("sr_build", os.path.join(_HERE, "csrc", "build.py"))
 
 
 def lib():
-    """Load (once) and return the ctypes library.  The binary must have been built from the sources lying next to it
-    (sr_source_hash() == hash of csrc/*.hip, headers, build flags): a missing or stale library is rebuilt when hipcc is there
-    and refused otherwise -- it is never loaded silently (a stale .so was tested once: commit e818dd3)."""
+    """Load (once) and return the ctypes library, by the rules of _native.load (sr_source_hash() == hash of csrc/*.hip, headers,
+    build flags)."""
     global _lib
     if _lib is None and _DEV_LIB:
-        L = C.CDLL(_DEV_LIB)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _native.bind(C.CDLL(_DEV_LIB), SYMBOLS)
     if _lib is None:
-        bm = _build_module()
-        want = bm.source_hash()
-        # Fast path without writing anything (a read-only install, or a current libsr_hip.so shipped without the git-ignored
-        # _obj/src.hash sidecar): the library in-tree already carries the hash of these sources.
-        # (found by looking for the hash string in the file's bytes: dlopen'ing a stale image would pin it in this process)
-        L = None
-        if os.path.exists(LIB_PATH) and bm.built_hash() in (None, want):
-            try:
-                with open(LIB_PATH, "rb") as f:
-                    current = want.encode() in f.read()
-                if current:
-                    L = _load()
-            except (OSError, AttributeError):
-                L = None
-        if L is None:
-            # One builder at a time (ranks of bench --gpus N, spawned test workers and parallel pytest all land here with the same
-            # stale hash): the lock covers the hash check, the compile into csrc/_obj and the rename of the linked file.
-            import fcntl
-            try:
-                os.makedirs(os.path.join(_HERE, "csrc", "_obj"), exist_ok=True)
-                lock = open(os.path.join(_HERE, "csrc", "_obj", ".build.lock"), "w")
-            except OSError as e:
-                raise SrHipError(f"libsr_hip.so is stale or missing (sources are {want}) and {os.path.join(_HERE, 'csrc')} is not "
-                                 f"writable for a rebuild: {e}; there is no CPU fallback for the product path") from e
-            with lock:
-                fcntl.flock(lock, fcntl.LOCK_EX)
-                try:
-                    have = bm.built_hash()
-                    if have != want:
-                        if os.environ.get("SR_NO_REBUILD") == "1":
-                            raise SrHipError(f"libsr_hip.so is stale or missing (built from {have}, sources are {want}) and SR_NO_REBUILD=1; "
-                                             "there is no CPU fallback for the product path")
-                        try:
-                            bm.build()
-                        except Exception as e:         # no hipcc, compile error: there is no CPU fallback for the product path
-                            raise SrHipError(f"libsr_hip.so is stale or missing (built from {have}, sources are {want}) and the rebuild "
-                                             f"failed: {e}\nrun `python stable-renderer_amd/csrc/build.py`; there is no CPU fallback for the "
-                                             "product path") from e
-                    if not os.path.exists(LIB_PATH):
-                        raise SrHipError(f"{LIB_PATH} not built; there is no CPU fallback for the product path")
-                    L = _load()
-                finally:
-                    fcntl.flock(lock, fcntl.LOCK_UN)
-        if L.sr_source_hash().decode() != want:
-            raise SrHipError(f"libsr_hip.so (built from {L.sr_source_hash().decode()}) does not match its sources ({want}): "
-                             "remove stable-renderer_amd/csrc/_obj and rebuild")
-        _lib = L
+        _lib = _native.load(LIB_PATH, SYMBOLS, _build_module(), "sr_source_hash", "python stable-renderer_amd/csrc/build.py")
     return _lib
 
 
 def check(rc):
     if rc != 0:
-        raise SrHipError("libsr_hip: %s (code %d)" % (lib().sr_last_error().decode(errors="replace"), rc))
+        _native.fail(rc, "libsr_hip", lib().sr_last_error())

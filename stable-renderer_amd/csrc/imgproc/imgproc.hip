@@ -1,36 +1,18 @@
 // The image and mask filters of ComfyUI's comfy_extras/nodes_post_processing.py (Blur, Sharpen, Blend) and comfy_extras/nodes_mask.py
-// (composite(), GrowMask, FeatherMask, MaskComposite, ImageColorToMask).  A library of its own (libsr_imgproc.so, C ABI in
-// include/sr_imgproc.h), like libsr_tiled.so and libsr_resample.so: the sources of libsr_hip.so -- and with them the identity its
-// recorded results are stamped with -- stay alone.
-#include <hip/hip_runtime.h>
+// (composite(), GrowMask, FeatherMask, MaskComposite, ImageColorToMask).  libsr_imgproc.so, C ABI in include/sr_imgproc.h; why it
+// is a library of its own: csrc/sidelib.py.
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include "../../../include/sr_imgproc.h"
-
+#define SR_SIDE imgproc
+#define SR_SIDE_UC IMGPROC
 #ifndef SR_IMGPROC_SRC_HASH
 #define SR_IMGPROC_SRC_HASH "unstamped"
 #endif
-
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* sr_imgproc_last_error(void) { return g_err; }
-extern "C" const char* sr_imgproc_source_hash(void) { return SR_IMGPROC_SRC_HASH; }
-#define SR_FAIL(code, ...) do { set_error(__VA_ARGS__); return (code); } while (0)
-#define SR_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
-    set_error("%s: %s", name, hipGetErrorString(e_)); return SR_IMGPROC_ERR_LAUNCH; } } while (0)
-#define SR_ERR_INVALID SR_IMGPROC_ERR_INVALID
-#define SR_OK SR_IMGPROC_OK
+#include "../sr_side.h"
 
 namespace {
 
-inline hipStream_t sr_stream(void* s) { return (hipStream_t)s; }
 constexpr int kThreads = 256;
 constexpr int64_t kMaxElems = (int64_t)1 << 31;              // a flat 1-D grid of 256-thread blocks stays below 2^23 blocks
 constexpr int32_t kMaxSide = 1 << 24;

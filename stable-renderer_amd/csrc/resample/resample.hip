@@ -1,36 +1,18 @@
 // comfy.utils.common_upscale (comfyUI/comfy/utils.py:418-443): F.interpolate in five modes, bislerp (utils.py:335-409) and the 8-bit
-// Lanczos of utils.py:411-416.  A library of its own (libsr_resample.so, C ABI in include/sr_resample.h), like libsr_tiled.so:
-// bandwidth-bound, output-stationary kernels that leave the sources of libsr_hip.so -- and with them the identity its recorded
-// results are stamped with -- alone.
-#include <hip/hip_runtime.h>
+// Lanczos of utils.py:411-416: bandwidth-bound, output-stationary kernels.  libsr_resample.so, C ABI in include/sr_resample.h; why
+// it is a library of its own: csrc/sidelib.py.
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include "../../../include/sr_resample.h"
-
+#define SR_SIDE resample
+#define SR_SIDE_UC RESAMPLE
 #ifndef SR_RESAMPLE_SRC_HASH
 #define SR_RESAMPLE_SRC_HASH "unstamped"
 #endif
-
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* sr_resample_last_error(void) { return g_err; }
-extern "C" const char* sr_resample_source_hash(void) { return SR_RESAMPLE_SRC_HASH; }
-#define SR_FAIL(code, ...) do { set_error(__VA_ARGS__); return (code); } while (0)
-#define SR_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
-    set_error("%s: %s", name, hipGetErrorString(e_)); return SR_RESAMPLE_ERR_LAUNCH; } } while (0)
-#define SR_ERR_INVALID SR_RESAMPLE_ERR_INVALID
-#define SR_OK SR_RESAMPLE_OK
+#include "../sr_side.h"
 
 namespace {
 
-inline hipStream_t sr_stream(void* s) { return (hipStream_t)s; }
 struct Strides { int64_t n, c, y, x; };                      // in elements
 inline Strides strides_of(const int64_t* s) { return Strides{s[0], s[1], s[2], s[3]}; }
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

@@ -1,37 +1,20 @@
 // Tiled VAE (comfy/utils.py:448-475 tiled_scale; comfy/sd.py:302-327 decode_tiled_ / encode_tiled_): the tile cut, the feathered
-// blend, the three-pass average, and a row softmax with a valid-column count for padded score matrices.  A library of its
-// own (libsr_tiled.so, C ABI in include/sr_tiled.h): bandwidth-bound helpers around the launch plans of libsr_hip.so, whose sources --
-// and with them the identity its recorded results are stamped with -- they leave alone.
-#include <hip/hip_runtime.h>
+// blend, the three-pass average, and a row softmax with a valid-column count for padded score matrices: bandwidth-bound helpers
+// around the launch plans of libsr_hip.so.  libsr_tiled.so, C ABI in include/sr_tiled.h; why it is a library of its own:
+// csrc/sidelib.py.
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include "../../../include/sr_tiled.h"
-
+#define SR_SIDE tiled
+#define SR_SIDE_UC TILED
 #ifndef SR_TILED_SRC_HASH
 #define SR_TILED_SRC_HASH "unstamped"
 #endif
-
-static thread_local char g_err[512] = "";
-static void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* sr_tiled_last_error(void) { return g_err; }
-extern "C" const char* sr_tiled_source_hash(void) { return SR_TILED_SRC_HASH; }
-#define SR_FAIL(code, ...) do { set_error(__VA_ARGS__); return (code); } while (0)
-#define SR_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
-    set_error("%s: %s", name, hipGetErrorString(e_)); return SR_TILED_ERR_LAUNCH; } } while (0)
-#define SR_ERR_INVALID SR_TILED_ERR_INVALID
-#define SR_OK SR_TILED_OK
+#include "../sr_side.h"
 #define SR_F16 SR_TILED_F16
 
 namespace {
 
-inline hipStream_t sr_stream(void* s) { return (hipStream_t)s; }
 __device__ __forceinline__ float sr_load_f(const float* p) { return *p; }
 __device__ __forceinline__ float sr_load_f(const _Float16* p) { return (float)*p; }
 __device__ __forceinline__ void sr_store_f(float* p, float v) { *p = v; }

@@ -1,11 +1,13 @@
-"""The ctypes mirror (_lib.py, _lib_tiled.py, _lib_resample.py) against the C headers it restates by hand (include/sr_hip.h,
-sr_tiled.h, sr_resample.h).  No GPU and no library needed: only the headers, the host C compiler and the Python tables.
+"""The ctypes mirror (_lib.py, _lib_tiled.py, _lib_resample.py, _lib_imgproc.py) against the C headers it restates by hand
+(include/sr_hip.h, sr_tiled.h, sr_resample.h, sr_imgproc.h).  No GPU and no library needed: only the headers, the host C compiler and the Python tables.
 
 * structs: a generated C program prints sizeof of every struct, offsetof + size of every member (the members of sr_op's union
   as ``u.ln.x`` and so on), the enumerators and the integer macros; these are compared with ctypes.sizeof, Field.offset / .size
   and the Python constants.  Every header struct must have a mirror and every mirror field a header member of the same name.
 * functions: the prototypes are parsed and compared with the SYMBOLS tables: the same names both ways, the same arity, and per
-  argument / return value the same class among pointer, int32, int64, float, double.
+  argument / return value the same class among pointer, int32, int64, float, double.  Each side library's header (SIDE) is also
+  read the plain way, every `sr_name(` outside a comment: that set, the parsed prototypes and the table must be one set of the
+  recorded size.
 * the checker itself is run over mutated header text and mutated tables: each mutation must be reported."""
 import ctypes as C
 import os
@@ -13,15 +15,18 @@ import re
 import shutil
 import subprocess
 
+import pytest
 
 from stable_renderer_amd import _lib as L
+from stable_renderer_amd import _lib_imgproc as LI
 from stable_renderer_amd import _lib_resample as LR
 from stable_renderer_amd import _lib_tiled as LT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
-HEADERS = ("sr_hip.h", "sr_tiled.h", "sr_resample.h")
-TABLES = {"sr_hip.h": L.SYMBOLS, "sr_tiled.h": LT.SYMBOLS, "sr_resample.h": LR.SYMBOLS}
+HEADERS = ("sr_hip.h", "sr_tiled.h", "sr_resample.h", "sr_imgproc.h")
+TABLES = {"sr_hip.h": L.SYMBOLS, "sr_tiled.h": LT.SYMBOLS, "sr_resample.h": LR.SYMBOLS, "sr_imgproc.h": LI.SYMBOLS}
+SIDE = {"sr_tiled.h": 6, "sr_resample.h": 5, "sr_imgproc.h": 9}              # header -> number of exported functions
 MIRRORS = {"sr_igemm_args": L.IgemmArgs, "sr_groupnorm_args": L.GroupNormArgs, "sr_attention_args": L.AttentionArgs, "sr_op": L.Op,
            "sr_draw": L.Draw, "sr_gbuffer": L.GBuffer}
 
@@ -364,6 +369,18 @@ def test_function_tables_match_the_prototypes():
     for h in HEADERS:
         probs += function_problems(parse(headers[h]).protos, TABLES[h], h)
     assert probs == []
+
+
+@pytest.mark.parametrize("header", sorted(SIDE))
+def test_side_header_declares_exactly_its_table(header):
+    """declared == bound, both ways, comments stripped; the library-specific halves (the symbols resolve, bad arguments are refused
+    with their texts) are in test_tiled_ref.py, test_resample_ref.py and test_imgproc_ref.py"""
+    text = read_headers()[header]
+    declared = set(re.findall(r"\b(sr_[a-z0-9_]+)\s*\(", strip(text)))
+    protos = parse(text).protos
+    assert declared == set(TABLES[header]) == set(protos) and len(declared) == SIDE[header]
+    assert function_problems(protos, TABLES[header], header) == []
+    assert parse(text).structs == {}                            # no structs cross these ABIs
 
 
 def _sub(text, old, new):
