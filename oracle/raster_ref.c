@@ -18,6 +18,10 @@
  *     clip-space (x, y, w) matrix evaluated at the pixel's NDC centre (Olano & Greer), inclusive edges, the same
  *     perspective-correct interpolation -- over the whole viewport; all three at w <= 0: dropped.  No GL output exists for
  *     such triangles in the reference (its scenes keep geometry in front of the camera): this path is defined here;
+ *   - guard band: a triangle with all three clip w > 0 takes the fixed-point path only if all six of its window coordinates
+ *     satisfy |s| <= GUARD = 2^25 pixels; otherwise (a vertex a hair in front of the eye: the divide by a tiny w throws it
+ *     millions of pixels out, or to inf / NaN) it takes the same homogeneous path as a triangle with a vertex behind the eye,
+ *     which never divides by a vertex's w (see GUARD below);
  *   - barycentrics b_i = (float)E_i / (float)area, perspective-correct attributes sum(a_i b_i/w_i) / sum(b_i/w_i)
  *     in the association order written below, window depth z = sum(z_i b_i), GL_LESS against a 1.0-cleared buffer;
  *   - flat vertexID = last vertex of the triangle (GL provoking vertex), textures sampled NEAREST with REPEAT (a diffuse
@@ -174,6 +178,14 @@ static void run_vertex(const ref_draw* d, int idx, vtx* o) {
   o->vid = d->vertex_id ? d->vertex_id[idx] : idx;
 }
 
+/* Guard band of the fixed-point path, in pixels.  With |s| <= 2^25: s * 16 is exact and |s * 16 + 0.5| rounds to at most 2^29,
+ * so to_fixed converts a float that is inside int range (beyond it the conversion is undefined in C and differs between CPUs
+ * and the GPU) and |fixed coordinate| <= 2^29; every int difference in edge() / top_left() / the bbox (two coordinates, or a
+ * coordinate and a pixel centre x * 16 + 8 of an image below 2^25 pixels a side, or +-15) stays below 2^30 + 2^29 < 2^31 and
+ * cannot wrap; every int64 product is below 2^61 and a difference of two below 2^62 < 2^63.  The comparison is written so that
+ * NaN and inf fail it. */
+#define GUARD 33554432.0f /* 2^25 */
+static int in_guard(float s) { return fabsf(s) <= GUARD; }
 static int to_fixed(float v) { return (int)floorf(v * 16.0f + 0.5f); }
 static int64_t edge(int ax, int ay, int bx, int by, int px, int py) {
   return (int64_t)(bx - ax) * (int64_t)(py - ay) - (int64_t)(by - ay) * (int64_t)(px - ax);
@@ -201,8 +213,9 @@ void ref_raster_draw(const ref_draw* d, ref_gbuffer* g) {
     for (int k = 0; k < 3; ++k) run_vertex(d, d->tris[3 * t + k], &v[k]);
     const int nfront = (v[0].cw > 0.0f) + (v[1].cw > 0.0f) + (v[2].cw > 0.0f);
     if (nfront == 0) continue;
-    const int homog = nfront < 3;
+    int homog = nfront < 3;
     int fx[3] = {0, 0, 0}, fy[3] = {0, 0, 0}; float z[3] = {0, 0, 0}, iw[3] = {0, 0, 0};
+    float sx[3] = {0, 0, 0}, sy[3] = {0, 0, 0};
     int sgn = 1, tl[3] = {0, 0, 0}; float farea = 1.0f;
     int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
     float E[9];
@@ -210,11 +223,14 @@ void ref_raster_draw(const ref_draw* d, ref_gbuffer* g) {
       for (int k = 0; k < 3; ++k) {
         iw[k] = 1.0f / v[k].cw;
         float nx = v[k].cx * iw[k], ny = v[k].cy * iw[k], nz = v[k].cz * iw[k];
-        float sx = (nx * 0.5f + 0.5f) * (float)W;
-        float sy = (1.0f - (ny * 0.5f + 0.5f)) * (float)H;
+        sx[k] = (nx * 0.5f + 0.5f) * (float)W;
+        sy[k] = (1.0f - (ny * 0.5f + 0.5f)) * (float)H;
         z[k] = nz * 0.5f + 0.5f;
-        fx[k] = to_fixed(sx); fy[k] = to_fixed(sy);
+        if (!(in_guard(sx[k]) && in_guard(sy[k]))) homog = 1;      /* outside the guard band: homogeneous path below */
       }
+    }
+    if (!homog) {
+      for (int k = 0; k < 3; ++k) { fx[k] = to_fixed(sx[k]); fy[k] = to_fixed(sy[k]); }
       int64_t area = edge(fx[0], fy[0], fx[1], fy[1], fx[2], fy[2]);
       if (area == 0) continue;
       /* GL front face = counter-clockwise as seen on screen; with y pointing DOWN in these window coordinates a visually

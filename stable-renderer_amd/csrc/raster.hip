@@ -3,7 +3,9 @@
 // texture copies (engine/static/texture/texture.py:166-254): the six G-buffer planes are plain HBM tensors.
 //
 //   raster_setup : one thread per triangle — vertex stage (default_Gbuffer.vert.glsl:40-57) for its three vertices,
-//                  28.4 fixed-point snapping, integer edge setup, pixel bbox; writes a 256-byte TriRec.
+//                  28.4 fixed-point snapping, integer edge setup, pixel bbox; writes a 256-byte TriRec.  A triangle with a
+//                  vertex at clip w <= 0, or with a window coordinate outside the guard band |s| <= 2^25 px (a vertex a hair
+//                  in front of the eye), gets the homogeneous edge setup instead.
 //   raster_tiles : one 256-thread workgroup per 16x16 pixel tile, one thread per pixel.  The workgroup walks the
 //                  draw's triangles in index order, bins the ones whose bbox touches the tile into LDS (ballot +
 //                  prefix compaction keeps primitive order; the bounding boxes come from a dense 16-byte-per-triangle array
@@ -27,7 +29,8 @@ constexpr float PI_F = 3.14159265359f;
 constexpr float CANNY_THRESHOLD = 0.17364817766693041f;   // cos(PI*4/9)
 constexpr int NON_AI_OBJ_MAP_INDEX = 2048;
 
-// valid = 2: a triangle with one or two vertices at clip w <= 0, rasterised in homogeneous coordinates (oracle/raster_ref.c header):
+// valid = 2: a triangle with one or two vertices at clip w <= 0, or with all three in front but a window coordinate outside the
+// guard band (GUARD below), rasterised in homogeneous coordinates (oracle/raster_ref.c header):
 // fx, fy, z then hold the nine inverse-matrix coefficients E (as float bits), iw the clip z and pad[0..2] the clip w of the vertices
 struct __attribute__((aligned(16))) TriRec {
   int x0, x1, y0, y1;                     // pixel bbox (inclusive), first so the binning pass reads one int4
@@ -133,6 +136,11 @@ __device__ __noinline__ void tex_trilinear(const float* tex, int w, int h, int l
 #pragma unroll
   for (int k = 0; k < 4; ++k) o[k] = c1[k] * (1.0f - fr) + c2[k] * fr;
 }
+// Guard band of the fixed-point path, in pixels (oracle/raster_ref.c GUARD, where the bound is derived): within it to_fixed is
+// exact and inside int range, no int difference in edge_fn / top_left / the bbox can wrap and no long long product can overflow.
+// The comparison is written so that NaN and inf fail it.
+constexpr float GUARD = 33554432.0f;      // 2^25
+__device__ __forceinline__ bool in_guard(float s) { return fabsf(s) <= GUARD; }
 __device__ __forceinline__ int to_fixed(float v) { return (int)floorf(v * 16.0f + 0.5f); }
 __device__ __forceinline__ long long edge_fn(int ax, int ay, int bx, int by, int px, int py) {
   return (long long)(bx - ax) * (long long)(py - ay) - (long long)(by - ay) * (long long)(px - ax);
@@ -165,16 +173,22 @@ __global__ void raster_setup(const sr_draw d, TriRec* __restrict__ recs, int W, 
     if (k == 2) r.vid = d.vertex_id ? d.vertex_id[idx] : idx;         // flat: provoking (last) vertex
   }
   const int nfront = (cw[0] > 0.0f) + (cw[1] > 0.0f) + (cw[2] > 0.0f);
-  if (nfront == 3) {
+  bool homog = nfront < 3;
+  float sx[3], sy[3];
+  if (!homog) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       r.iw[k] = 1.0f / cw[k];
       const float nx = cx[k] * r.iw[k], ny = cy[k] * r.iw[k], nz = cz[k] * r.iw[k];
-      const float sx = (nx * 0.5f + 0.5f) * (float)W;
-      const float sy = (1.0f - (ny * 0.5f + 0.5f)) * (float)H;
+      sx[k] = (nx * 0.5f + 0.5f) * (float)W;
+      sy[k] = (1.0f - (ny * 0.5f + 0.5f)) * (float)H;
       r.z[k] = nz * 0.5f + 0.5f;
-      r.fx[k] = to_fixed(sx); r.fy[k] = to_fixed(sy);
+      if (!(in_guard(sx[k]) && in_guard(sy[k]))) homog = true;      // outside the guard band: homogeneous path below
     }
+  }
+  if (!homog) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { r.fx[k] = to_fixed(sx[k]); r.fy[k] = to_fixed(sy[k]); }
     const long long area = edge_fn(r.fx[0], r.fy[0], r.fx[1], r.fy[1], r.fx[2], r.fy[2]);
     // GL front face = visually counter-clockwise = NEGATIVE area in these y-down window coordinates
     if (area != 0 && !(area > 0 && d.cull_back)) {
@@ -190,7 +204,7 @@ __global__ void raster_setup(const sr_draw d, TriRec* __restrict__ recs, int W, 
       r.farea = (float)((long long)sgn * area);
       r.valid = (r.x0 <= r.x1 && r.y0 <= r.y1) ? 1 : 0;
     }
-  } else if (nfront > 0) {
+  } else if (nfront > 0) {                // (overwrites the iw / z of a triangle the guard band sent here)
     float cof[9];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
