@@ -9,6 +9,10 @@ of touching it, and sr_side.h, not sr_common.h, is their shared prologue.
 
 A new side library is one entry here, one .hip, one header under include/ and one SYMBOLS table bound by _native.SideLibrary.
 
+PRIVATE holds the side libraries whose ABI only this package calls (no call site in the reference, nothing for INTEGRATION.md to
+describe): their header lies next to the source, not under include/, and their binding module is not named _lib_*.py.  They are
+built, hashed and loaded by the same rules; every function here resolves a name in either table.
+
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
 import hashlib
 import importlib.util
@@ -25,17 +29,30 @@ REGISTRY = {
     "resample": ("resample", "resample.hip", "sr_resample.h", "SR_RESAMPLE_SRC_HASH"),
     "imgproc": ("imgproc", "imgproc.hip", "sr_imgproc.h", "SR_IMGPROC_SRC_HASH"),
 }
+# name -> (directory, source, private header next to the source, hash macro)
+PRIVATE = {
+    "ksteps": ("ksteps", "ksteps.hip", "sr_ksteps.h", "SR_KSTEPS_SRC_HASH"),
+}
+
+
+def entry(name):
+    """-> (directory, source, path of the header, hash macro) of a public or a private side library"""
+    if name in REGISTRY:
+        d, src, hdr, macro = REGISTRY[name]
+        return d, src, os.path.join(HERE, "..", "..", "include", hdr), macro
+    d, src, hdr, macro = PRIVATE[name]
+    return d, src, os.path.join(HERE, d, hdr), macro
 
 
 def lib_path(name):
-    return os.path.join(HERE, REGISTRY[name][0], "libsr_%s.so" % name)
+    return os.path.join(HERE, entry(name)[0], "libsr_%s.so" % name)
 
 
 def source_hash(name):
-    """sha256 over the source, its public header, the shared prologue and this file (the flags live here)"""
-    d, src, hdr, _ = REGISTRY[name]
+    """sha256 over the source, its header (wherever it lies), the shared prologue and this file (the flags live here)"""
+    d, src, hdr, _ = entry(name)
     h = hashlib.sha256()
-    for fp in (os.path.join(HERE, d, src), os.path.join(HERE, "..", "..", "include", hdr), os.path.join(HERE, SHARED), os.path.abspath(__file__)):
+    for fp in (os.path.join(HERE, d, src), hdr, os.path.join(HERE, SHARED), os.path.abspath(__file__)):
         h.update(os.path.basename(fp).encode())
         with open(fp, "rb") as fh:
             h.update(fh.read())
@@ -58,7 +75,7 @@ def hipcc():
 
 
 def build(name, force=False):
-    d, src, _, macro = REGISTRY[name]
+    d, src, _, macro = entry(name)
     lib = lib_path(name)
     if force or not is_current(name):
         tmp = lib + ".tmp%d" % os.getpid()
@@ -73,5 +90,5 @@ def build(name, force=False):
 
 
 if __name__ == "__main__":
-    for n in [a for a in sys.argv[1:] if a != "--force"] or list(REGISTRY):
+    for n in [a for a in sys.argv[1:] if a != "--force"] or list(REGISTRY) + list(PRIVATE):
         print(build(n, force="--force" in sys.argv))

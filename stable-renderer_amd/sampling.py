@@ -3,7 +3,7 @@ meaning: ``ModelSamplingDiscrete`` (comfyUI/comfy/model_sampling.py:75-150), ``c
 ``KSampler`` (comfy/samplers.py:415-451, 937-1078), ``calc_cond_uncond_batch`` + ``sampling_function`` (batch =
 [uncond | cond], CFG; samplers.py:176-358), ``BaseModel.apply_model`` with EPS scaling (comfy/model_base.py:93-127),
 the k-diffusion loops ``sample_euler`` / ``sample_ddpm`` / ``sample_lcm`` (comfy/k_diffusion/sampling.py:129-149,
-749-793) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
+749-793; the eight further samplers of ksamplers.py are driven from here) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
 once on the host; everything per step (UNet plan, CFG, sampler update, latent overlap) runs as HIP kernels.
 """
 import math
@@ -11,6 +11,7 @@ import os
 
 import torch
 
+from . import ksamplers as KS
 from . import ops as O
 
 LATENT_SCALE = 0.18215            # comfy/latent_formats.py SD15.scale_factor
@@ -22,7 +23,11 @@ def latent_scale_of(unet_cfg):
     (comfy/supported_models.py:153-175 SDXL / SDXLRefiner -> latent_formats.SDXL), everything else here is SD1.x / SD2.x"""
     return LATENT_SCALE_SDXL if unet_cfg.get("adm_in_channels") else LATENT_SCALE
 SCHEDULER_NAMES = ["normal", "karras", "exponential", "sgm_uniform", "simple", "ddim_uniform"]
-SAMPLER_NAMES = ["euler", "ddim", "ddpm", "lcm"]
+SAMPLER_NAMES = ["euler", "ddim", "ddpm", "lcm"] + list(KS.NAMES)
+# names of the reference's list (comfy/samplers.py:692-697) that are not built: the SDE family draws from torchsde's Brownian tree,
+# the others are solvers of their own kind.  Selecting one is an error, not an Euler picture.
+UNBUILT_SAMPLER_NAMES = ["dpm_fast", "dpm_adaptive", "dpmpp_sde", "dpmpp_sde_gpu", "dpmpp_2m_sde", "dpmpp_2m_sde_gpu", "dpmpp_3m_sde",
+                         "dpmpp_3m_sde_gpu", "uni_pc", "uni_pc_bh2"]
 
 
 # view shard: replay the cut plan segments as hipGraphs?  "1" / "0" decide; unset = eagerly for one call at a time, as graphs once
@@ -128,21 +133,32 @@ class SamplingCallbackContext:
 
 class KSampler:
     """Schedule holder (comfy/samplers.py:954-1003).  ``timesteps`` is NOT re-sliced when denoise < 1, exactly as in
-    the reference (samplers.py:1000-1003 vs types/runtime.py:585-588)."""
+    the reference (samplers.py:1000-1003 vs types/runtime.py:585-588).  A name outside the reference's list falls back to
+    euler as there (samplers.py:969-972); a name of its list that is not built here raises."""
 
     def __init__(self, steps, sampler="euler", scheduler="normal", denoise=None, model_sampling=None):
         self.ms = model_sampling or ModelSamplingDiscrete()
+        if sampler in UNBUILT_SAMPLER_NAMES:
+            raise NotImplementedError(f"sampler '{sampler}' is not built (built: {', '.join(SAMPLER_NAMES)})")
         self.sampler_name = sampler if sampler in SAMPLER_NAMES else SAMPLER_NAMES[0]
         self.scheduler = scheduler if scheduler in SCHEDULER_NAMES else SCHEDULER_NAMES[0]
         self.steps = steps
         if denoise is None or denoise > 0.9999:
-            self.sigmas = calculate_sigmas_scheduler(self.ms, self.scheduler, steps)
-            self.timesteps = [int(self.ms.timestep(s)) for s in self.sigmas]
+            self.sigmas, self.timesteps = self.calculate_sigmas(steps)
         else:
             new_steps = int(steps / denoise)
-            sig = calculate_sigmas_scheduler(self.ms, self.scheduler, new_steps)
-            self.timesteps = [int(self.ms.timestep(s)) for s in sig]
+            sig, self.timesteps = self.calculate_sigmas(new_steps)
             self.sigmas = sig[-(steps + 1):]
+
+    def calculate_sigmas(self, steps):
+        """KSampler.calculate_sigmas (samplers.py:979-992): dpm_2 and dpm_2_ancestral are scheduled with one step more and lose
+        the sigma before the final 0; the timesteps keep it, as there"""
+        discard = self.sampler_name in KS.DISCARD_PENULTIMATE_SIGMA
+        sig = calculate_sigmas_scheduler(self.ms, self.scheduler, steps + 1 if discard else steps)
+        timesteps = [int(self.ms.timestep(s)) for s in sig]
+        if discard:
+            sig = torch.cat([sig[:-2], sig[-1:]])
+        return sig, timesteps
 
 
 class DiffusionRunner:
@@ -396,9 +412,11 @@ class DiffusionRunner:
                     cp["prologue"].run()
         return G
 
-    def _general_denoise(self, sigma, timestep_index, want_d):
-        """one sampling_function call (samplers.py:323-358) over the prepared groups -> self.den (and self.d)"""
+    def _general_denoise(self, sigma, timestep_index, want_d, x=None, den=None, d=None):
+        """one sampling_function call (samplers.py:323-358) over the prepared groups -> self.den (and self.d); the samplers of
+        ksamplers.py evaluate other latents than self.x into other buffers (x, den, d)"""
         G = self._general
+        x, den, d = self.x if x is None else x, self.den if den is None else den, self.d if d is None else d
         self._general_select(sigma)
         G["out_c"].zero_()
         G["out_u"].zero_()
@@ -406,7 +424,7 @@ class DiffusionRunner:
         G["cnt_u"].fill_(1e-37)
         for g in G["groups"]:
             p = g["plan"]
-            O.cond_crop_scale(self.x, p["x"], g["area"], g["chunks"], sigma)
+            O.cond_crop_scale(x, p["x"], g["area"], g["chunks"], sigma)
             p["t"].fill_(float(timestep_index))
             if p.get("cn") is not None:
                 self._run_controls(p, sigma)
@@ -414,10 +432,9 @@ class DiffusionRunner:
                 self._sharded_eval(p, chunks=g["chunks"])
             else:
                 p["step"].run()
-            O.cond_accumulate(self.x, p["out"], g["mult"], g["kinds"], G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], g["area"],
+            O.cond_accumulate(x, p["out"], g["mult"], g["kinds"], G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], g["area"],
                               g["chunks"], sigma)
-        O.cfg_combine(self.x, G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], self.den, self.d if want_d else None, sigma,
-                      self.cfg_scale)
+        O.cfg_combine(x, G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], den, d if want_d else None, sigma, self.cfg_scale)
 
     def _load_ctx(self, p):
         N = self.N
@@ -450,10 +467,10 @@ class DiffusionRunner:
                     hb[c * N:(c + 1) * N].copy_(hv.expand(N, -1, -1, -1) if hv.shape[0] == 1 else hv)
                 cp["prologue"].run()                        # hint encoder: once per run
 
-    def model_eps(self, p, sigma, timestep_index):
+    def model_eps(self, p, sigma, timestep_index, x=None):
         """calc_cond_uncond_batch + apply_model: xin = x/sqrt(sigma^2+1) for both chunks, t = argmin|log sigma|"""
         n = self.x.numel()
-        O.eps_scale_input(self.x, p["x"], self.copies, sigma)
+        O.eps_scale_input(self.x if x is None else x, p["x"], self.copies, sigma)
         p["t"].fill_(float(timestep_index))
         if p.get("cn") is not None:                         # ControlNet encoders on the same (x, t, ctx), then their merge; no
             self._run_controls(p, sigma)                    # cross-view work inside them (controlnet.py:205-213 passes no corresponder)
@@ -530,6 +547,39 @@ class DiffusionRunner:
         self._comm_events = []
         return ms
 
+    def _run_ksampler(self, sampler, ks, p, noise_fn, predrawn, step_callback, pre_step_callback):
+        """the loop of one of ksamplers.py's samplers over this runner: self.x is the latent, `evaluate` is the model call plus CFG
+        on any latent at any sigma (timestep, ControlNets and, on the general path, the active entries of THAT sigma), slot 0 is
+        self.den / self.d and the further slots are allocated here on first use (p: the plan of the plain path, None = general)"""
+        sig = ks.sigmas
+        ws = getattr(self, "_ks_ws", None)
+        if ws is None:
+            ws = self._ks_ws = KS.Workspace(self.x)
+        state = {"step": -1}
+
+        def evaluate(x, sigma, slot):
+            den, d = (self.den, self.d) if slot == 0 else (ws.get(f"den{slot}"), ws.get(f"d{slot}"))
+            if x is self.x:                                     # a step's first evaluation
+                state["step"] += 1
+                if pre_step_callback is not None:
+                    pre_step_callback(self.x, state["step"], ks.timesteps[state["step"]])
+            t_idx = int(self.ms.timestep(sigma))
+            if p is None:
+                self._general_denoise(sigma, t_idx, True, x=x, den=den, d=d)
+            else:
+                eps = self.model_eps(p, sigma, t_idx, x=x)
+                O.cfg_denoise(x, eps, den, d, self.copies, sigma, self.cfg_scale)
+            return den, d
+
+        def callback(i, x, den):
+            step_callback(SamplingCallbackContext(x, i, den, len(sig) - 1, ks.timesteps, sig.tolist()))
+        if sampler == "heunpp2":
+            # its per-step draw is torch.randn_like(x) on the global generator, whatever noise sampler the caller has; the
+            # numbers are dropped (s_churn = 0), so they are not sent to the device
+            def noise_fn():
+                return predrawn.pop(0) if predrawn is not None else torch.randn(tuple(self.x.shape), dtype=torch.float32)
+        KS.DRIVERS[sampler](evaluate, noise_fn, self.x, sig, callback if step_callback is not None else None, ws)
+
     def sample(self, noise, steps, sampler_name, scheduler, denoise=1.0, latent_image=None, seed=None,
                inject_n_rand=None, step_callback=None, noise_fn=None, rng_turn=None, pre_step_callback=None):
         """-> samples (N,4,h,w) fp32 on device (already divided by the latent scale, samplers.py:933).
@@ -544,6 +594,9 @@ class DiffusionRunner:
         sig = ks.sigmas
         sampler = ks.sampler_name
         dev = self.x.device
+        if sampler in KS.DRIVERS and self.shard is not None and self.shard.active:
+            # their second and third evaluations of a step have no rehearsed collective schedule
+            raise NotImplementedError(f"sampler '{sampler}' is not available on a view shard: use euler, ddim, ddpm or lcm")
         # rng_turn: context manager that admits concurrent callers in call order (pipeline.CallOrder) around the draws on the
         # process-wide CPU generator, so calls in flight on several streams draw exactly what the sequential loop draws
         import contextlib
@@ -581,13 +634,15 @@ class DiffusionRunner:
             predrawn = None
             if rng_turn is not None and noise_fn is None and sampler in ("ddpm", "lcm"):
                 predrawn = [torch.randn(tuple(self.x.shape), dtype=torch.float32) for i in range(len(sig) - 1) if float(sig[i + 1]) > 0]
+            elif rng_turn is not None and (noise_fn is None or sampler == "heunpp2") and sampler in KS.DRIVERS:
+                predrawn = [torch.randn(tuple(self.x.shape), dtype=torch.float32) for _ in range(KS.noise_draws(sampler, sig))]
         latent = torch.zeros_like(noise) if latent_image is None else latent_image * self.latent_scale
         max_denoise = math.isclose(float(self.ms.sigma_max), float(sig[0]), rel_tol=1e-05) or float(sig[0]) > float(self.ms.sigma_max)
         s0 = float(torch.sqrt(1.0 + sig[0] ** 2.0)) if max_denoise else float(sig[0])
         self.x.copy_(noise.to(dev, torch.float32))
         O.axpby(self.x, latent.to(dev, torch.float32).contiguous(), 1.0, s0)        # x = noise*s0 + latent
         if general:
-            self._general_plans(inject, [float(v) for v in sig[:-1]])
+            self._general_plans(inject, [float(v) for v in sig[:-1]] + (KS.extra_sigmas(sampler, sig) if sampler in KS.DRIVERS else []))
             p = G["groups"][0]["plan"]
         else:
             p = self._ensure_plan(inject)
@@ -599,7 +654,9 @@ class DiffusionRunner:
             def noise_fn():
                 return torch.randn(tuple(self.x.shape), dtype=torch.float32).to(dev)    # default_noise_sampler (CPU x)
         t_index = [int(t) for t in self.ms.timestep(sig[:-1])]          # ModelSamplingDiscrete.timestep, once per run
-        for i in range(len(sig) - 1):
+        if sampler in KS.DRIVERS:
+            self._run_ksampler(sampler, ks, p if not general else None, noise_fn, predrawn, step_callback, pre_step_callback)
+        for i in range(len(sig) - 1) if sampler not in KS.DRIVERS else ():
             s, sn = float(sig[i]), float(sig[i + 1])
             if pre_step_callback is not None:
                 pre_step_callback(self.x, i, ks.timesteps[i])
