@@ -369,7 +369,12 @@ int sr_corrmap_update(const float* frame, int32_t Cf, const int32_t* ids, const 
  * pixels ((2r+1)-pixel clamped DIAGONAL pooling, overlap.py:69-76), forms the weighted mean (algo 0 average, 1 frame
  * distance, 2 pixel distance, 3 view normal incl. the reference's column-sum-per-row normalisation) and blends with alpha;
  * keep_nonzero: ResizeOverlap's where(ovlp != 0, ovlp, orig).  Jacobi form: reads x, writes y (the reference updates in
- * place in dict order, which only differs for radius > 0).  x,y: (T,C,h,w) fp32; pix_vert: (T*H*W) vertex index or -1. */
+ * place in dict order, which only differs for radius > 0).  x,y: (T,C,h,w) fp32; pix_vert: (T*H*W) vertex index or -1.
+ * The unchanged value and the (1 - alpha) term of cell (i,j) are the UP-SAMPLED latent at the sampled pixel (the cell that pixel
+ * up-samples from; (i,j) itself only at integer ratios H/h, W/w), and cell (i,j) is what keep_nonzero keeps: the reference's
+ * nearest up -> overlap -> nearest down -> where, also off integer ratios and for h > H.
+ * SR_ERR_INVALID (nothing written): a null pointer (tr_* may point anywhere valid when no pixel carries an id: they are not
+ * read), C outside 1..8, a size < 1, radius < 0, algo outside 0..3, algo 3 without view_normal. */
 int sr_legacy_overlap(const float* x, float* y, const int32_t* pix_vert, const int32_t* offsets, const int32_t* tr_f,
                       const int32_t* tr_y, const int32_t* tr_x, const float* view_normal, int32_t T, int32_t C, int32_t h,
                       int32_t w, int32_t H, int32_t W, float alpha, int32_t radius, int32_t algo, int32_t keep_nonzero,

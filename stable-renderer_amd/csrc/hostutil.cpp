@@ -10,7 +10,8 @@
 // Vertices seen once never write (overlap.py:122-126): they get level -1.  All pointers are HOST memory.
 extern "C" int sr_legacy_levels(const int32_t* offsets, const int32_t* tr_f, const int32_t* tr_y, const int32_t* tr_x, const int32_t* order,
                                 int32_t n_vertices, int32_t T, int32_t H, int32_t W, int32_t radius, int32_t* level_of, int32_t* n_levels) {
-  if (!offsets || !tr_f || !tr_y || !tr_x || !order || !level_of || !n_levels || radius < 0) SR_FAIL(SR_ERR_INVALID, "sr_legacy_levels: bad args");
+  if (!offsets || !tr_f || !tr_y || !tr_x || !order || !level_of || !n_levels || radius < 0 || n_vertices < 0 || T < 1 || H < 1 || W < 1)
+    SR_FAIL(SR_ERR_INVALID, "sr_legacy_levels: bad args");
   const size_t npx = (size_t)T * H * W;
   std::vector<int32_t> wl(npx, -1), rl(npx, -1);
   int32_t top = -1;

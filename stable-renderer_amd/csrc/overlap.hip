@@ -369,7 +369,9 @@ __global__ void corrmap_pass2(const float* __restrict__ frame, int Cf, const int
   writtens[cell] = 1;
 }
 
-// legacy Overlap / ResizeOverlap fused at latent resolution: one thread per output cell
+// legacy Overlap / ResizeOverlap fused at latent resolution: one thread per output cell.  Cell (i,j) samples map pixel (py,px); what
+// the reference down-samples there is the UP-SAMPLED latent, i.e. cell_of_px(py,px) -- which is (i,j) only while H/h and W/w are
+// integers -- so the unchanged value and the (1 - alpha) term come from that cell, and cell (i,j) itself only where the result is 0.
 __global__ void legacy_overlap_kernel(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ pix_vert,
                                       const int* __restrict__ offsets, const int* __restrict__ tr_f, const int* __restrict__ tr_y,
                                       const int* __restrict__ tr_x, const float* __restrict__ vn, int T, int C, int h, int w, int H, int W,
@@ -385,16 +387,20 @@ __global__ void legacy_overlap_kernel(const float* __restrict__ x, float* __rest
   float* yo = y + (int64_t)f * C * lhw + (int64_t)i * w + j;
   const int v = pix_vert[((int64_t)f * H + py) * W + px];
   const int b = v >= 0 ? offsets[v] : 0, e = v >= 0 ? offsets[v + 1] : 0;
-  if (v < 0 || e - b < 2) {                                   // no id / vertex seen once: unchanged
-    for (int c = 0; c < C; ++c) yo[c * lhw] = xf[c * lhw + (int64_t)i * w + j];
-    return;
-  }
   // up-sampled latent value of full-res pixel (yy,xx) of frame ff: nearest up-sampling = cell (floor(yy*h/H), floor(xx*w/W))
   const float uy = (float)h / (float)H, ux = (float)w / (float)W;
   auto cell_of_px = [&](int yy, int xx) -> int64_t {
     const int ci = min((int)floorf((float)yy * uy), h - 1), cj = min((int)floorf((float)xx * ux), w - 1);
     return (int64_t)ci * w + cj;
   };
+  const int64_t here = (int64_t)i * w + j, up = cell_of_px(py, px);
+  if (v < 0 || e - b < 2) {                                   // no id / vertex seen once: the up-sampled latent, unchanged
+    for (int c = 0; c < C; ++c) {
+      const float val = xf[c * lhw + up];
+      yo[c * lhw] = (keep_nonzero && val == 0.0f) ? xf[c * lhw + here] : val;
+    }
+    return;
+  }
   // which trace entry is this pixel?  (the one with the same (f,py,px))
   int me = b;
   for (int t = b; t < e; ++t) if (tr_f[t] == f && tr_y[t] == py && tr_x[t] == px) { me = t; break; }
@@ -422,9 +428,8 @@ __global__ void legacy_overlap_kernel(const float* __restrict__ x, float* __rest
   if (algo == 3) norm = (float)(e - b) * (1.0f / (fabsf(1.0f - my_vn) + 1.0f));   // column sum of w[.,me] applied to row me
   (void)me;
   for (int c = 0; c < C && c < 8; ++c) {
-    const float orig = xf[c * lhw + (int64_t)i * w + j];
-    const float val = alpha * (acc[c] / norm) + (1.0f - alpha) * orig;
-    yo[c * lhw] = (keep_nonzero && val == 0.0f) ? orig : val;
+    const float val = alpha * (acc[c] / norm) + (1.0f - alpha) * xf[c * lhw + up];
+    yo[c * lhw] = (keep_nonzero && val == 0.0f) ? xf[c * lhw + here] : val;
   }
 }
 
@@ -504,7 +509,8 @@ extern "C" int sr_legacy_overlap(const float* x, float* y, const int32_t* pix_ve
                                  int32_t w, int32_t H, int32_t W, float alpha, int32_t radius, int32_t algo, int32_t keep_nonzero,
                                  void* stream) {
   if (!x || !y || !pix_vert || !offsets || !tr_f || !tr_y || !tr_x) SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap: null");
-  if (C > 8 || radius < 0 || algo < 0 || algo > 3 || (algo == 3 && !view_normal)) SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap: bad args");
+  if (T < 1 || C < 1 || C > 8 || h < 1 || w < 1 || H < 1 || W < 1 || radius < 0 || algo < 0 || algo > 3 || (algo == 3 && !view_normal))
+    SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap: bad args");
   hipLaunchKernelGGL(legacy_overlap_kernel, g1((int64_t)T * h * w), dim3(256), 0, sr_stream(stream), x, y, pix_vert, offsets, tr_f, tr_y, tr_x,
                      view_normal, T, C, h, w, H, W, alpha, radius, algo, keep_nonzero);
   SR_CHECK_LAUNCH("sr_legacy_overlap");
@@ -516,7 +522,8 @@ extern "C" int sr_legacy_overlap_seq(float* U, float* newval, const int32_t* lvl
                                      const float* view_normal, int32_t C, int32_t H, int32_t W, float alpha, int32_t radius, int32_t algo,
                                      void* stream) {
   if (!U || !newval || !lvl_vert || !lvl_off_host || !offsets || !tr_f || !tr_y || !tr_x) SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap_seq: null");
-  if (C > 8 || radius < 0 || algo < 0 || algo > 3 || (algo == 3 && !view_normal) || max_len < 1) SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap_seq: bad args");
+  if (C < 1 || C > 8 || H < 1 || W < 1 || n_levels < 0 || radius < 0 || algo < 0 || algo > 3 || (algo == 3 && !view_normal) || max_len < 1)
+    SR_FAIL(SR_ERR_INVALID, "sr_legacy_overlap_seq: bad args");
   hipStream_t st = sr_stream(stream);
   for (int l = 0; l < n_levels; ++l) {
     const int b = lvl_off_host[l], n = lvl_off_host[l + 1] - b;

@@ -95,6 +95,8 @@ class CorrespondenceMap:
         in-place order at this kernel radius (sr_legacy_levels; built once per radius)"""
         import ctypes as C
         import numpy as np
+        if radius not in self._levels and self.n_vertices == 0:                # no pixel carries an id: nothing to schedule
+            self._levels[radius] = (torch.empty(0, dtype=torch.int32, device=self.pix_vert.device), np.zeros(1, np.int32), 0)
         if radius not in self._levels:
             off, f, y, x, order = (t.cpu().numpy() for t in (self.offsets, self.tr_f, self.tr_y, self.tr_x, self.order))
             lvl = np.empty(max(self.n_vertices, 1), np.int32)
@@ -108,6 +110,11 @@ class CorrespondenceMap:
             lvl_off = np.concatenate([[0], np.cumsum(np.bincount(lvl[active], minlength=nl.value))]).astype(np.int32)
             self._levels[radius] = (torch.from_numpy(by_level).to(self.pix_vert.device), lvl_off, int(nl.value))
         return self._levels[radius]
+
+    def trace_ptrs(self):
+        """tr_f / tr_y / tr_x for the C entry points.  When no pixel carries an id they are empty tensors without storage: the
+        entry points refuse NULL, and the kernels read no trace then, so the (never empty) offsets stand in for them"""
+        return [O._p(t if t.numel() else self.offsets) for t in (self.tr_f, self.tr_y, self.tr_x)]
 
     @property
     def size(self):
@@ -136,8 +143,8 @@ class Overlap:
             if view_normal_map is None:
                 raise TypeError("overlap() missing 1 required positional argument: 'view_normal_map'")
             vn = view_normal_map.reshape(T, corr_map.height, corr_map.width).contiguous().float().to(xin.device)
-        L.check(L.lib().sr_legacy_overlap(O._p(xin), O._p(y), O._p(corr_map.pix_vert), O._p(corr_map.offsets), O._p(corr_map.tr_f),
-                                          O._p(corr_map.tr_y), O._p(corr_map.tr_x), O._p(vn), T, C, h, w, corr_map.height, corr_map.width,
+        L.check(L.lib().sr_legacy_overlap(O._p(xin), O._p(y), O._p(corr_map.pix_vert), O._p(corr_map.offsets), *corr_map.trace_ptrs(),
+                                          O._p(vn), T, C, h, w, corr_map.height, corr_map.width,
                                           float(alpha), int(radius), self.algorithm.algo, self.keep_nonzero, O.stream_ptr()))
         return y.reshape(T, 1, C, h, w)
 
@@ -162,8 +169,8 @@ class Overlap:
         if n_levels > 0:
             newval = torch.empty(int(corr_map.offsets[-1]) * Cc, dtype=torch.float32, device=xin.device)
             L.check(lib.sr_legacy_overlap_seq(O._p(U), O._p(newval), O._p(lvl_vert), lvl_off.ctypes.data_as(C.c_void_p), n_levels,
-                                              corr_map.max_len, O._p(corr_map.offsets), O._p(corr_map.tr_f), O._p(corr_map.tr_y),
-                                              O._p(corr_map.tr_x), O._p(vn), Cc, H, W, float(alpha), int(radius), self.algorithm.algo, st))
+                                              corr_map.max_len, O._p(corr_map.offsets), *corr_map.trace_ptrs(), O._p(vn), Cc, H, W,
+                                              float(alpha), int(radius), self.algorithm.algo, st))
         if (h, w) == (H, W):
             return U
         y = torch.empty_like(xin)
@@ -178,7 +185,8 @@ class Overlap:
 
 class ResizeOverlap(Overlap):
     """latents are (conceptually) resized to the corr-map size, overlapped and resized back (overlap.py:155-222).  With the default
-    ``nearest`` the kernel does all three at latent resolution; ``bilinear``, ``bicubic``, ``area`` and ``nearest-exact`` resample up
+    ``nearest`` the kernel does all three at latent resolution (also where H/h or W/w is no integer, or h > H: the round trip then
+    moves cells, as the reference's does); ``bilinear``, ``bicubic``, ``area`` and ``nearest-exact`` resample up
     (sr_resample), run the full-resolution overlap and resample down, composed as the reference composes them."""
     keep_nonzero = 1
     interpolate_modes = ('nearest', 'bilinear', 'bicubic', 'area', 'nearest-exact')
