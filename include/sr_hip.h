@@ -45,11 +45,12 @@ typedef struct {
   const void* a;          /* [B, H, W, C1] activations (dtype)                                        */
   const void* a2;         /* optional [B, H, W, C2] second source (decoder skip concat) or NULL        */
   const void* w;          /* packed weights [Npad, KH*KH*(C1+C2)] dtype, K contiguous, Npad%128==0     */
-  const float* bias;      /* [N] fp32 or NULL                                                          */
+  const float* bias;      /* [N] fp32 or NULL; fetched in 16-byte chunks: readable up to N rounded up to 4 floats */
   const float* rowvec;    /* [B, N] fp32 added per batch entry (time embedding) or NULL                */
   const void* residual;   /* [M, N] dtype or NULL (ignored when transpose_out)                         */
   void* out;              /* [M, N] (or [B, N, ldt] when transpose_out) dtype, fp32 when out_f32       */
-  const void* zero_page;  /* >= 16 bytes of zeros (source for padding taps / rows >= M)                 */
+  const void* zero_page;  /* zeros, at least max(C1, C2) elements of dtype and >= 16 bytes: padding taps and rows >= M
+                             read it at the K offset of the source row they stand in for                */
   int32_t B, H, W;        /* input batch and spatial size                                              */
   int32_t C1, C2;         /* channels of a / a2 (multiples of 64 for fp16, 32 for fp32)                */
   int32_t N;              /* valid output channels (N of the GEMM; for GEGLU the 2*inner interleaved)  */
@@ -74,7 +75,7 @@ typedef struct {
                              W' = W * gamma (per k), colsum[n] = sum_k W'[n,k], bias' = bias + W . beta: the GEMM reads
                              the un-normalised rows and the normalised tensor is never materialised
                              (BasicTransformerBlock norm1/2/3 -> to_q/k/v, ff.net.0, attention.py:521-654)          */
-  const float* colsum;    /* [N] fp32, required with row_stats                                                     */
+  const float* colsum;    /* [N] fp32 (readable up to N rounded up to 4 floats, as bias), required with row_stats  */
   int32_t tile;           /* 0 = library heuristic; 1 = 256x128 (8 waves, 3-stage), 2 = 128x128, 3 = 128x64, 4 = 64x64,
                              5 = 256x320 (fp16, N % 320 == 0; 2 LDS stages of 128-byte K-steps), 6 = 256x320 with a 4-deep ring of
                              64-byte K-steps, 7 = 128x320 (8 waves, for half as many pixels), 8 = patch-stationary 3x3 (256x320; fp16, KH 3,
@@ -249,7 +250,24 @@ int sr_graph_destroy(void* graph_exec);
  * Plans: "prologue" (prompt-only work: cross-attention K / V, label_emb; run when ctx changes) and "step" (one evaluation).
  * Inputs / outputs by name: UNet "x" (B,4,h,w) fp32, "t" (B,) fp32, "ctx" (B,n_ctx,ctx_dim) in the model dtype, optional "y",
  * "inject" (n_rand int32 batch indices of the K/V-injected frames), "out" (B,4,h,w) fp32; VAE "z" (N,4,h,w) fp32, "img" (N,H,W,3) fp32.
- * sr_model_write / sr_model_read / sr_unet_forward / sr_vae_decode accept host OR device pointers (hipMemcpyDefault). */
+ * sr_model_write / sr_model_read / sr_unet_forward / sr_vae_decode accept host OR device pointers (hipMemcpyDefault).
+ *
+ * What sr_model_load guarantees about a file it accepts (the file is not trusted; stable-renderer_amd/csrc/bundle_file.h, a host-only
+ * reader, judges ALL of it before the first byte is allocated on the device, and every refusal is SR_ERR_INVALID with a message
+ * naming plan, op and field):
+ *   addresses  every pointer a kernel receives is (a tensor the loader allocated) + (an offset inside it): relocations name pointer
+ *              fields of their op's kind only, each at most once, with offset < the tensor's size (offset 0 of an empty tensor
+ *              is legal), and a pointer field no relocation names must be NULL in the file;
+ *   extents    through every relocated pointer, offset + the bytes the op touches <= the tensor's size, the bytes restated from
+ *              the contracts in this header and the op's own counts (B, H, W, C1, N, ldt, rows, n, workspace_bytes ...; packed
+ *              weights count Npad rows, bias / colsum N rounded up to 4 floats, the zero page one K-row): a flipped size is refused at
+ *              load, it never runs;
+ *   shape      op kinds are the 15 of sr_op_kind, lanes 0 / 1; counts the entry points refuse (negative, an unknown dtype ...)
+ *              are refused, for ops no relocation names too; io windows lie inside their tensors, and "inject_err" is 4 bytes;
+ *   memory     the tensor sizes add up (without overflow) to no more than the current device's total memory.
+ * What it does NOT: the format has no checksum.  Corrupted CONTENTS (weights, norm parameters, index tensors) and changed fields
+ * that are neither pointers nor sizes (scale, act, eps, silu, tile, split, group ...) load and compute something else, or are
+ * refused by the entry point at run time; whether the device has that much memory FREE is found out by hipMalloc (SR_ERR_LAUNCH). */
 typedef struct sr_model sr_model;
 int sr_model_load(const char* path, sr_model** model);
 int sr_model_free(sr_model* model);

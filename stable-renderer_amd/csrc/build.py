@@ -15,7 +15,7 @@ EXTRA = {"raster.hip": ["-ffp-contract=off"],
          # softmax row maxima never see a NaN (masked scores are -inf, every tile has a valid key): drop the canonicalising
          # v_max x,x the compiler otherwise adds around every fmaxf in the VALU-bound loop
          "attention.hip": ["-fno-honor-nans"]}
-HEADERS = ["sr_common.h", os.path.join("..", "..", "include", "sr_hip.h")]
+HEADERS = ["sr_common.h", "bundle_file.h", os.path.join("..", "..", "include", "sr_hip.h")]
 
 
 def hipcc():

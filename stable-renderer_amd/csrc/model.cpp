@@ -16,6 +16,7 @@
 //   plans[n_plans]     : char name[16], u32 n_ops, u32 n_reloc, u32 sizeof_op, u32 pad,
 //                        ops[n_ops * sizeof_op], reloc[n_reloc] = { u32 op, u32 field_offset, u32 tensor, u32 pad, u64 offset }
 #include "sr_common.h"
+#include "bundle_file.h"
 #include <stddef.h>
 #include <stdio.h>
 #include <string.h>
@@ -24,8 +25,7 @@
 #include <vector>
 
 namespace {
-struct Io { char name[32]; uint32_t tensor, is_output; uint64_t offset, nbytes; };
-struct Reloc { uint32_t op, field, tensor, pad; uint64_t offset; };
+using sr_bundle::Io;
 struct PlanRec { char name[16]; std::vector<sr_op> ops; };
 }  // namespace
 
@@ -38,134 +38,65 @@ struct sr_model {
   bool prologue_ran = false;                                 // sr_unet_forward(ctx = NULL) needs a projected prompt
 };
 
-static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
-
-// byte offsets (inside sr_op) of every device-pointer field of an op of this kind
-static std::vector<size_t> pointer_fields(int kind) {
-#define F(member, field) (offsetof(sr_op, u) + offsetof(decltype(sr_op::u), member) + offsetof(decltype(decltype(sr_op::u)::member), field))
-  switch (kind) {
-    case SR_OP_IGEMM: return {F(igemm, a), F(igemm, a2), F(igemm, w), F(igemm, bias), F(igemm, rowvec), F(igemm, residual), F(igemm, out),
-                              F(igemm, zero_page), F(igemm, workspace), F(igemm, row_stats), F(igemm, colsum), F(igemm, prefetch), F(igemm, split_counters)};
-    case SR_OP_GROUPNORM: return {F(gn, x), F(gn, x2), F(gn, gamma), F(gn, beta), F(gn, y), F(gn, partials)};
-    case SR_OP_ATTENTION: return {F(attn, q), F(attn, k), F(attn, vt), F(attn, o)};
-    case SR_OP_LAYERNORM: case SR_OP_ROW_STATS: return {F(ln, x), F(ln, gamma), F(ln, beta), F(ln, y)};
-    case SR_OP_LAYERNORM_GATHER: return {F(ln, x), F(ln, gamma), F(ln, beta), F(ln, y), F(ln, sel), F(ln, err_flag)};
-    case SR_OP_NCHW_TO_NHWC: case SR_OP_NHWC_TO_NCHW: return {F(cvt, x), F(cvt, y), F(cvt, per_batch_scale)};
-    case SR_OP_TIMESTEP_EMBED: return {F(temb, t), F(temb, y)};
-    case SR_OP_SILU: case SR_OP_SOFTMAX_ROWS: return {F(ew, x), F(ew, y)};
-    case SR_OP_GATHER_ROWS: return {F(gather, x), F(gather, y), F(gather, sel), F(gather, err_flag)};
-    case SR_OP_ADD_SCALED: return {F(add, a), F(add, b), F(add, y)};
-    default: return {};
-  }
-#undef F
-}
-
 static void free_model(sr_model* m) {
   if (!m) return;
   for (void* p : m->tensors) if (p) (void)hipFree(p);
   delete m;
 }
 
+// The file is not trusted, and nothing of it reaches the device before ALL of it has been judged: sr_bundle::read (bundle_file.h,
+// host only) parses the head and checks every count, relocation, unrelocated pointer field, io window and -- through the sizes each
+// op carries -- every byte an op would touch through a relocated pointer against the tensor it points into, and the sum of the
+// tensor sizes against this device's memory.  Only then: allocate, zero or upload, patch the pointers in.  No address from the file
+// ever reaches a kernel, and no count from it lets a kernel leave the tensor its pointer was relocated into.
 extern "C" int sr_model_load(const char* path, sr_model** out) {
   if (!path || !out) SR_FAIL(SR_ERR_INVALID, "sr_model_load: null argument");
   *out = nullptr;
-  FILE* f = fopen(path, "rb");
-  if (!f) SR_FAIL(SR_ERR_INVALID, "sr_model_load: cannot open %s", path);
-  char magic[8];
-  uint32_t hdr[4];
-  if (!rd(f, magic, 8) || memcmp(magic, "SRMODEL1", 8) != 0 || !rd(f, hdr, sizeof(hdr)) || hdr[0] != 1) {
-    fclose(f);
-    SR_FAIL(SR_ERR_INVALID, "sr_model_load: %s is not a version-1 model bundle", path);
-  }
-  const uint32_t nt = hdr[1], nio = hdr[2], np = hdr[3];
-  // the file is not trusted: every count is bounded by what a file of this size can hold before anything is allocated
-  long fsize = 0;
-  if (fseek(f, 0, SEEK_END) != 0 || (fsize = ftell(f)) < 24 || fseek(f, 24, SEEK_SET) != 0 ||
-      (uint64_t)nt * 16 + (uint64_t)nio * sizeof(Io) + (uint64_t)np * 32 > (uint64_t)fsize) {
-    fclose(f);
-    SR_FAIL(SR_ERR_INVALID, "sr_model_load: %s: header counts (%u tensors, %u io, %u plans) do not fit the file", path, nt, nio, np);
-  }
+  size_t mem_free = 0, mem_total = 0;
+  if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_total == 0) SR_FAIL(SR_ERR_LAUNCH, "sr_model_load: hipMemGetInfo failed");
   sr_model* m = nullptr;
+  FILE* f = nullptr;
   try {
+  sr_bundle::Bundle b;
+  std::string err;
+  if (sr_bundle::read(path, (uint64_t)mem_total, &b, &err) != SR_OK) SR_FAIL(SR_ERR_INVALID, "%s", err.c_str());
+  const size_t nt = b.tensors.size();
   m = new sr_model();
   (void)hipGetDevice(&m->device);
-  std::vector<uint64_t> data_off(nt);
-  m->sizes.resize(nt);
   m->tensors.assign(nt, nullptr);
-  bool ok = true;
-  for (uint32_t i = 0; i < nt && ok; ++i) { uint64_t v[2]; ok = rd(f, v, sizeof(v)); m->sizes[i] = v[0]; data_off[i] = v[1]; }
-  m->io.resize(nio);
-  for (uint32_t i = 0; i < nio && ok; ++i) ok = rd(f, &m->io[i], sizeof(Io));
-  std::vector<std::vector<Reloc>> relocs(np);
-  m->plans.resize(np);
-  for (uint32_t i = 0; i < np && ok; ++i) {
-    uint32_t ph[4];
-    ok = rd(f, m->plans[i].name, 16) && rd(f, ph, sizeof(ph));
-    if (ok && ph[2] != sizeof(sr_op)) {
-      fclose(f); free_model(m);
-      SR_FAIL(SR_ERR_INVALID, "sr_model_load: bundle built for sizeof(sr_op) = %u, this library has %zu (re-export it)", ph[2], sizeof(sr_op));
-    }
-    if (!ok) break;
-    if ((uint64_t)ph[0] * sizeof(sr_op) + (uint64_t)ph[1] * sizeof(Reloc) > (uint64_t)fsize) { ok = false; break; }
-    m->plans[i].ops.resize(ph[0]);
-    relocs[i].resize(ph[1]);
-    ok = (ph[0] == 0 || rd(f, m->plans[i].ops.data(), (size_t)ph[0] * sizeof(sr_op))) && (ph[1] == 0 || rd(f, relocs[i].data(), (size_t)ph[1] * sizeof(Reloc)));
-  }
-  if (!ok) { fclose(f); free_model(m); SR_FAIL(SR_ERR_INVALID, "sr_model_load: %s is truncated", path); }
+  m->sizes.resize(nt);
+  for (size_t i = 0; i < nt; ++i) m->sizes[i] = b.tensors[i].nbytes;
+  m->io = b.io;
   // ---- tensors: allocate, zero or upload
+  f = fopen(path, "rb");
+  if (!f) { free_model(m); SR_FAIL(SR_ERR_INVALID, "sr_model_load: cannot open %s", path); }
   std::vector<char> stage;
-  for (uint32_t i = 0; i < nt; ++i) {
+  for (size_t i = 0; i < nt; ++i) {
     const uint64_t nb = m->sizes[i] ? m->sizes[i] : 16;
     if (hipMalloc(&m->tensors[i], nb) != hipSuccess) { fclose(f); free_model(m); SR_FAIL(SR_ERR_LAUNCH, "sr_model_load: hipMalloc of %llu bytes failed", (unsigned long long)nb); }
-    if (data_off[i] == 0) {
+    if (b.tensors[i].data_offset == 0) {
       if (hipMemset(m->tensors[i], 0, nb) != hipSuccess) { fclose(f); free_model(m); SR_FAIL(SR_ERR_LAUNCH, "sr_model_load: hipMemset failed"); }
     } else {
-      if (data_off[i] > (uint64_t)fsize || m->sizes[i] > (uint64_t)fsize - data_off[i]) {
-        fclose(f); free_model(m);
-        SR_FAIL(SR_ERR_INVALID, "sr_model_load: tensor %u of %s lies outside the file", i, path);
-      }
       stage.resize(m->sizes[i]);
-      if (fseek(f, (long)data_off[i], SEEK_SET) != 0 || !rd(f, stage.data(), m->sizes[i]) ||
+      if (fseek(f, (long)b.tensors[i].data_offset, SEEK_SET) != 0 || fread(stage.data(), 1, m->sizes[i], f) != m->sizes[i] ||
           hipMemcpy(m->tensors[i], stage.data(), m->sizes[i], hipMemcpyHostToDevice) != hipSuccess) {
         fclose(f); free_model(m);
-        SR_FAIL(SR_ERR_INVALID, "sr_model_load: cannot read / upload tensor %u of %s", i, path);
+        SR_FAIL(SR_ERR_INVALID, "sr_model_load: cannot read / upload tensor %zu of %s", i, path);
       }
     }
   }
   fclose(f);
   f = nullptr;
-  // ---- relocations: (tensor, offset) -> device pointer, written into the pointer field of the op.  A relocation must name a
-  // pointer field of that op's kind (pointer_fields: the table of them, from the struct definitions), and every pointer field
-  // that NO relocation names must be NULL in the file: no address from the file ever reaches a kernel.
-  for (uint32_t i = 0; i < np; ++i) {
-    std::vector<std::vector<bool>> hit(m->plans[i].ops.size());
-    for (const Reloc& r : relocs[i]) {
-      if (r.op >= m->plans[i].ops.size() || r.tensor >= nt || r.field + sizeof(void*) > sizeof(sr_op) || r.offset > m->sizes[r.tensor]) {
-        free_model(m);
-        SR_FAIL(SR_ERR_INVALID, "sr_model_load: bad relocation in plan %u", i);
-      }
-      const std::vector<size_t> pf = pointer_fields(m->plans[i].ops[r.op].kind);
-      size_t which = pf.size();
-      for (size_t k = 0; k < pf.size(); ++k) if (pf[k] == r.field) which = k;
-      if (which == pf.size()) { free_model(m); SR_FAIL(SR_ERR_INVALID, "sr_model_load: plan %u op %u: relocation of a non-pointer field", i, r.op); }
-      if (hit[r.op].empty()) hit[r.op].assign(pf.size(), false);
-      hit[r.op][which] = true;
-      char* field = (char*)&m->plans[i].ops[r.op] + r.field;
+  // ---- relocations (all validated above): (tensor, offset) -> device pointer, written into the pointer field of the op
+  m->plans.resize(b.plans.size());
+  for (size_t i = 0; i < b.plans.size(); ++i) {
+    memcpy(m->plans[i].name, b.plans[i].name, sizeof(m->plans[i].name));
+    m->plans[i].ops.swap(b.plans[i].ops);
+    for (const sr_bundle::Reloc& r : b.plans[i].relocs) {
       void* ptr = (char*)m->tensors[r.tensor] + r.offset;
-      memcpy(field, &ptr, sizeof(void*));
-    }
-    for (size_t o = 0; o < m->plans[i].ops.size(); ++o) {
-      const std::vector<size_t> pf = pointer_fields(m->plans[i].ops[o].kind);
-      for (size_t k = 0; k < pf.size(); ++k) {
-        if (!hit[o].empty() && hit[o][k]) continue;
-        void* v = nullptr;
-        memcpy(&v, (const char*)&m->plans[i].ops[o] + pf[k], sizeof(void*));
-        if (v) { free_model(m); SR_FAIL(SR_ERR_INVALID, "sr_model_load: plan %u op %zu carries a raw address in an unrelocated pointer field", i, o); }
-      }
+      memcpy((char*)&m->plans[i].ops[r.op] + r.field, &ptr, sizeof(void*));
     }
   }
-  for (const Io& e : m->io)
-    if (e.tensor >= nt || e.offset > m->sizes[e.tensor] || e.nbytes > m->sizes[e.tensor] - e.offset) { free_model(m); SR_FAIL(SR_ERR_INVALID, "sr_model_load: bad io window"); }
   } catch (const std::bad_alloc&) {                          // (never through the extern "C" frame)
     if (f) fclose(f);
     free_model(m);

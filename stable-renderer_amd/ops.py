@@ -63,10 +63,15 @@ def pack_conv_weight(w, dtype, cin_pad=None, geglu=False):
 
 
 def pack_bias(b, geglu=False):
+    """fp32 bias / colsum row of an igemm, zero-padded to a multiple of 4 floats: the kernels fetch it in 16-byte chunks, one at
+    every n = 4c < N (sr_igemm_args.bias), so the last chunk of an N that is no multiple of 4 (the VAE's conv_out, N = 3) reaches
+    past N"""
     b = b.float()
     if geglu:
         half = b.shape[0] // 2
         b = torch.stack([b[:half], b[half:]], dim=1).reshape(-1)
+    if b.shape[0] % 4:
+        b = torch.cat([b, b.new_zeros(-b.shape[0] % 4)])
     return b.contiguous()
 
 
