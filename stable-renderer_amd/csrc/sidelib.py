@@ -13,6 +13,9 @@ PRIVATE holds the side libraries whose ABI only this package calls (no call site
 describe): their header lies next to the source, not under include/, and their binding module is not named _lib_*.py.  They are
 built, hashed and loaded by the same rules; every function here resolves a name in either table.
 
+PRIVATE_NODES is a third table of the same form as PRIVATE, for the private libraries behind graph nodes (libsr_morph.so: Morphology
+and Porter-Duff compositing).  It exists because the contents of the two older tables are pinned by tests; names() lists all three.
+
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
 import hashlib
 import importlib.util
@@ -33,6 +36,15 @@ REGISTRY = {
 PRIVATE = {
     "ksteps": ("ksteps", "ksteps.hip", "sr_ksteps.h", "SR_KSTEPS_SRC_HASH"),
 }
+# name -> (directory, source, private header next to the source, hash macro)
+PRIVATE_NODES = {
+    "morph": ("morph", "morph.hip", "sr_morph.h", "SR_MORPH_SRC_HASH"),
+}
+
+
+def names():
+    """every side library: the three tables' names, in order"""
+    return list(REGISTRY) + list(PRIVATE) + list(PRIVATE_NODES)
 
 
 def entry(name):
@@ -40,7 +52,7 @@ def entry(name):
     if name in REGISTRY:
         d, src, hdr, macro = REGISTRY[name]
         return d, src, os.path.join(HERE, "..", "..", "include", hdr), macro
-    d, src, hdr, macro = PRIVATE[name]
+    d, src, hdr, macro = PRIVATE[name] if name in PRIVATE else PRIVATE_NODES[name]
     return d, src, os.path.join(HERE, d, hdr), macro
 
 
@@ -90,5 +102,5 @@ def build(name, force=False):
 
 
 if __name__ == "__main__":
-    for n in [a for a in sys.argv[1:] if a != "--force"] or list(REGISTRY) + list(PRIVATE):
+    for n in [a for a in sys.argv[1:] if a != "--force"] or names():
         print(build(n, force="--force" in sys.argv))

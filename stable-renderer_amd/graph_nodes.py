@@ -811,6 +811,74 @@ IMGPROC_NODES = {"ImageBlur": ImageBlur, "ImageSharpen": ImageSharpen, "ImageBle
                  "ThresholdMask": ThresholdMask}
 
 
+# ---- morphology and Porter-Duff compositing (comfy_extras/nodes_morphology.py, comfy_extras/nodes_compositing.py) over morph.py ----
+class Morphology:
+    """nodes_morphology.py:7-41"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "process"
+    CATEGORY = "image/postprocessing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "operation": (["erode", "dilate", "open", "close", "gradient", "bottom_hat", "top_hat"],),
+                             "kernel_size": _int(3, 3, 999)}}
+
+    def process(self, image, operation, kernel_size):
+        from . import morph as MP
+        return (MP.morphology(_dev(image), operation, kernel_size),)
+
+
+class PorterDuffImageComposite:
+    """nodes_compositing.py:92-142"""
+    RETURN_TYPES = ("IMAGE", "MASK")
+    FUNCTION = "composite"
+    CATEGORY = "mask/compositing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        from . import morph as MP
+        return {"required": {"source": ("IMAGE",), "source_alpha": ("MASK",), "destination": ("IMAGE",), "destination_alpha": ("MASK",),
+                             "mode": (list(MP.PD_MODES), {"default": "DST"})}}
+
+    def composite(self, source, source_alpha, destination, destination_alpha, mode):
+        from . import morph as MP
+        return MP.porter_duff_image_composite(_dev(source), _dev(source_alpha), _dev(destination), _dev(destination_alpha), mode)
+
+
+class SplitImageWithAlpha:
+    """nodes_compositing.py:145-162"""
+    RETURN_TYPES = ("IMAGE", "MASK")
+    FUNCTION = "split_image_with_alpha"
+    CATEGORY = "mask/compositing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",)}}
+
+    def split_image_with_alpha(self, image):
+        from . import morph as MP
+        return MP.split_image_with_alpha(_dev(image))
+
+
+class JoinImageWithAlpha:
+    """nodes_compositing.py:165-188"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "join_image_with_alpha"
+    CATEGORY = "mask/compositing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "alpha": ("MASK",)}}
+
+    def join_image_with_alpha(self, image, alpha):
+        from . import morph as MP
+        return (MP.join_image_with_alpha(_dev(image), _dev(alpha)),)
+
+
+MORPH_NODES = {"Morphology": Morphology, "PorterDuffImageComposite": PorterDuffImageComposite, "SplitImageWithAlpha": SplitImageWithAlpha,
+               "JoinImageWithAlpha": JoinImageWithAlpha}
+
+
 class LoadImage:
     """comfyUI/nodes.py:1623-1665 -> (IMAGE (1,H,W,3) in [0,1], MASK = 1 - alpha or 64x64 zeros).  ``image`` is a path, or a name
     under $SR_INPUT_DIR (the reference's input directory)"""
@@ -900,6 +968,9 @@ for _name, _cls in _X.ALL.items():
     register_node(_name, _cls)
 
 for _name, _cls in IMGPROC_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in MORPH_NODES.items():
     register_node(_name, _cls)
 
 
