@@ -16,6 +16,9 @@ built, hashed and loaded by the same rules; every function here resolves a name 
 PRIVATE_NODES is a third table of the same form as PRIVATE, for the private libraries behind graph nodes (libsr_morph.so: Morphology
 and Porter-Duff compositing).  It exists because the contents of the two older tables are pinned by tests; names() lists all three.
 
+PRIVATE_MODELS is a fourth table of the same form, for the private libraries that run a whole model (libsr_esrgan.so: the upscale
+models).  names() and the three older tables are pinned by tests, so all_names() = names() + this table is what builds everything.
+
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
 import hashlib
 import importlib.util
@@ -40,6 +43,10 @@ PRIVATE = {
 PRIVATE_NODES = {
     "morph": ("morph", "morph.hip", "sr_morph.h", "SR_MORPH_SRC_HASH"),
 }
+# name -> (directory, source, private header next to the source, hash macro)
+PRIVATE_MODELS = {
+    "esrgan": ("esrgan", "esrgan.hip", "sr_esrgan.h", "SR_ESRGAN_SRC_HASH"),
+}
 
 
 def names():
@@ -47,12 +54,22 @@ def names():
     return list(REGISTRY) + list(PRIVATE) + list(PRIVATE_NODES)
 
 
+def all_names():
+    """names() and the model libraries of PRIVATE_MODELS: everything sidelib builds"""
+    return names() + list(PRIVATE_MODELS)
+
+
 def entry(name):
     """-> (directory, source, path of the header, hash macro) of a public or a private side library"""
     if name in REGISTRY:
         d, src, hdr, macro = REGISTRY[name]
         return d, src, os.path.join(HERE, "..", "..", "include", hdr), macro
-    d, src, hdr, macro = PRIVATE[name] if name in PRIVATE else PRIVATE_NODES[name]
+    for table in (PRIVATE, PRIVATE_NODES, PRIVATE_MODELS):
+        if name in table:
+            d, src, hdr, macro = table[name]
+            break
+    else:
+        raise KeyError(name)
     return d, src, os.path.join(HERE, d, hdr), macro
 
 
@@ -102,5 +119,5 @@ def build(name, force=False):
 
 
 if __name__ == "__main__":
-    for n in [a for a in sys.argv[1:] if a != "--force"] or names():
+    for n in [a for a in sys.argv[1:] if a != "--force"] or all_names():
         print(build(n, force="--force" in sys.argv))

@@ -879,6 +879,40 @@ MORPH_NODES = {"Morphology": Morphology, "PorterDuffImageComposite": PorterDuffI
                "JoinImageWithAlpha": JoinImageWithAlpha}
 
 
+# ---- upscale models (comfy_extras/nodes_upscale_model.py) over esrgan.py ---------------------------------------------------------
+class UpscaleModelLoader:
+    """nodes_upscale_model.py:8-24 -> (UPSCALE_MODEL,): a registered state dict or a file under $SR_MODELS_DIR/upscale_models/"""
+    RETURN_TYPES = ("UPSCALE_MODEL",)
+    FUNCTION = "load_model"
+    CATEGORY = "loaders"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model_name": ("STRING", {})}}
+
+    def load_model(self, model_name):
+        from . import esrgan as ES
+        return (ES.load_upscale_model(WT.resolve("upscale_models", model_name)),)
+
+
+class ImageUpscaleWithModel:
+    """nodes_upscale_model.py:27-61: tiles of 512 with an overlap of 32, halved when memory runs out"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "upscale"
+    CATEGORY = "image/upscaling"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"upscale_model": ("UPSCALE_MODEL",), "image": ("IMAGE",)}}
+
+    def upscale(self, upscale_model, image):
+        from . import esrgan as ES
+        return (ES.upscale_image(upscale_model, _dev(image), tile=512, overlap=32),)
+
+
+UPSCALE_NODES = {"UpscaleModelLoader": UpscaleModelLoader, "ImageUpscaleWithModel": ImageUpscaleWithModel}
+
+
 class LoadImage:
     """comfyUI/nodes.py:1623-1665 -> (IMAGE (1,H,W,3) in [0,1], MASK = 1 - alpha or 64x64 zeros).  ``image`` is a path, or a name
     under $SR_INPUT_DIR (the reference's input directory)"""
@@ -971,6 +1005,9 @@ for _name, _cls in IMGPROC_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in MORPH_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in UPSCALE_NODES.items():
     register_node(_name, _cls)
 
 

@@ -3,13 +3,13 @@ comfyUI/nodes.py:554-573, 689-700, 770-783) and the LoRA merge they need.
 
 There is no network and no checkpoint in this image, so names resolve in this order: (1) a provider registered in-process
 (``register_checkpoint`` ...: tests and bench register seeded synthetic weights of the exact SD1.5 shapes), (2) a
-``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras}/<name>`` (the reference's folder_paths layout),
+``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras,upscale_models}/<name>`` (the reference's folder_paths layout),
 else FileNotFoundError.  Nothing here touches the GPU; tensors stay on the host until UNet / VAEDecoder pack them."""
 import os
 
 import torch
 
-_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}}
+_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}, "upscale_models": {}}
 
 
 def _norm(name):
@@ -29,6 +29,11 @@ def register_controlnet(name, provider):
 def register_lora(name, provider):
     """provider() -> {lora key: tensor}"""
     _REG["loras"][_norm(name)] = provider
+
+
+def register_upscale_model(name, provider):
+    """provider() -> the state dict of an upscale model (UpscaleModelLoader, comfy_extras/nodes_upscale_model.py:18-24)"""
+    _REG["upscale_models"][_norm(name)] = provider
 
 
 def clear_registry():
