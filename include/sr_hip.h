@@ -40,17 +40,27 @@ int sr_device_sync(void);                  /* hipDeviceSynchronize (tests only) 
  * convs (comfy/ldm/modules/diffusionmodules/model.py:541-650).
  * out[m, n] = act( scale * sum_k A[m,k] * Wt[n,k] + bias[n] + rowvec[b(m), n] ) + residual[m, n]
  *   m = (b, oy, ox) output pixel, k = (ky, kx, c) with c running over the channel concat [a | a2].
+ *
+ * Alignment (checked on the host: SR_ERR_INVALID before any launch): the kernels fetch a, a2, w and zero_page with 16-byte
+ * LDS-DMA requests, bias / colsum / rowvec as float4 and residual / out in 16-byte chunks, so each of those pointers must be a
+ * multiple of 16 bytes ("align 16" below); with a rowvec, rowvec_ld (when not 0) must be a multiple of 4 floats whenever N is.
+ * row_stats is read as float2 (align 8), workspace holds float4 partials (align 16), split_counters and prefetch are touched
+ * 4 bytes at a time (align 4).  Nothing more than that is assumed: a view into a wider tensor is a legal operand.
+ * Extents: every operand is read / written inside the extent stated at its field and nowhere else.  (Inside a tile the kernels
+ * may fetch bias / colsum chunks of columns >= N and weight rows in [N, Npad): those lie inside the stated extents.)
  */
 typedef struct {
-  const void* a;          /* [B, H, W, C1] activations (dtype)                                        */
-  const void* a2;         /* optional [B, H, W, C2] second source (decoder skip concat) or NULL        */
-  const void* w;          /* packed weights [Npad, KH*KH*(C1+C2)] dtype, K contiguous, Npad%128==0     */
-  const float* bias;      /* [N] fp32 or NULL; fetched in 16-byte chunks: readable up to N rounded up to 4 floats */
-  const float* rowvec;    /* [B, N] fp32 added per batch entry (time embedding) or NULL                */
-  const void* residual;   /* [M, N] dtype or NULL (ignored when transpose_out)                         */
-  void* out;              /* [M, N] (or [B, N, ldt] when transpose_out) dtype, fp32 when out_f32       */
+  const void* a;          /* [B, H, W, C1] activations (dtype); align 16                              */
+  const void* a2;         /* optional [B, H, W, C2] second source (decoder skip concat) or NULL; align 16 */
+  const void* w;          /* packed weights [Npad, KH*KH*(C1+C2)] dtype, K contiguous, Npad%128==0; align 16 */
+  const float* bias;      /* [N] fp32 or NULL; fetched in 16-byte chunks: readable up to N rounded up to 4 floats; align 16 */
+  const float* rowvec;    /* [B, N] fp32 added per batch entry (time embedding) or NULL; align 16; read up to
+                             (B - 1) * rowvec_ld + N floats                                            */
+  const void* residual;   /* [M, N] dtype or NULL (ignored when transpose_out); align 16               */
+  void* out;              /* [M, N] (or [B, N, ldt] when transpose_out) dtype, fp32 when out_f32; align 16.  Transposed: only
+                             columns [0, pixels per batch) of each row are written, [pixels, ldt) keep what they held */
   const void* zero_page;  /* zeros, at least max(C1, C2) elements of dtype and >= 16 bytes: padding taps and rows >= M
-                             read it at the K offset of the source row they stand in for                */
+                             read it at the K offset of the source row they stand in for; align 16      */
   int32_t B, H, W;        /* input batch and spatial size                                              */
   int32_t C1, C2;         /* channels of a / a2 (multiples of 64 for fp16, 32 for fp32)                */
   int32_t N;              /* valid output channels (N of the GEMM; for GEGLU the 2*inner interleaved)  */
@@ -68,14 +78,21 @@ typedef struct {
                              batched time-embedding projection                                         */
   void* workspace;        /* optional fp32 scratch for split-K (small-M convs of the 8x8 / 16x16 levels: too few
                              output tiles to fill 256 CUs).  NULL = never split.  May be shared by all ops
-                             of a stream; contents are dead after the call.                            */
+                             of a stream; contents are dead after the call.  align 16.
+                             Size: a split launch runs the tiles of whole rounds of workgroups unsplit and splits only the
+                             partly empty last round S ways.  With BM x BN the tile (2 and 15: 128 x 128, 3 and 14:
+                             128 x 64), tiles = ceil(M / BM) * ceil(N / BN), R the workgroups of a round (tile 2: 512, 3: 768,
+                             14 / 15: 256) and tail = tiles mod R, it needs   S * tail * BM * BN * 4   bytes (S fp32 partial
+                             tiles per tail tile) and touches nothing past them.  split = S with fewer bytes declared is
+                             SR_ERR_INVALID; split = 0 only considers the S that fit workspace_bytes (tile 0 chooses
+                             between the 128 x 128 and 128 x 64 forms of tiles 2 / 3 by the same formula).              */
   int64_t workspace_bytes;
-  const float* row_stats; /* optional [M, 2] fp32 (rstd, -rstd*mean) of the INPUT rows: LayerNorm folded into the GEMM --
+  const float* row_stats; /* optional [M, 2] fp32 (rstd, -rstd*mean) of the INPUT rows (align 8): LayerNorm folded into the GEMM --
                              out = rstd[m] * (x[m,:] . W'[n,:]) + (-rstd[m]*mean[m]) * colsum[n] + bias'[n] with
                              W' = W * gamma (per k), colsum[n] = sum_k W'[n,k], bias' = bias + W . beta: the GEMM reads
                              the un-normalised rows and the normalised tensor is never materialised
                              (BasicTransformerBlock norm1/2/3 -> to_q/k/v, ff.net.0, attention.py:521-654)          */
-  const float* colsum;    /* [N] fp32 (readable up to N rounded up to 4 floats, as bias), required with row_stats  */
+  const float* colsum;    /* [N] fp32 (readable up to N rounded up to 4 floats, as bias; align 16), required with row_stats  */
   int32_t tile;           /* 0 = library heuristic; 1 = 256x128 (8 waves, 3-stage), 2 = 128x128, 3 = 128x64, 4 = 64x64,
                              5 = 256x320 (fp16, N % 320 == 0; 2 LDS stages of 128-byte K-steps), 6 = 256x320 with a 4-deep ring of
                              64-byte K-steps, 7 = 128x320 (8 waves, for half as many pixels), 8 = patch-stationary 3x3 (256x320; fp16, KH 3,
@@ -97,12 +114,13 @@ typedef struct {
                              workgroup touches its share of them at kernel start (one 4-byte LDS-DMA read per 64 bytes, the data
                              is discarded), so they sit in the Infinity Cache when their layer starts instead of coming from HBM
                              on that layer's critical path (a UNet evaluation streams 1.7 GB of weights, far more than the
-                             256 MB cache keeps between evaluations).  NULL = none.  Never changes a result.                    */
+                             256 MB cache keeps between evaluations).  NULL = none.  Never changes a result.  align 4; reads
+                             stay inside [prefetch, prefetch + prefetch_bytes)                                                 */
   int64_t prefetch_bytes;
   int32_t up_h, up_w;     /* with upsample = 1: output size of the fused nearest upsample when it is not exactly 2H x 2W (0 = x2);
                              src = floor(dst * in/out) as F.interpolate(mode="nearest"): odd-sized latents (conditioning areas)
                              where Upsample.forward targets the skip tensor's size (openaimodel.py:109-121)                      */
-  int32_t* split_counters;/* optional: SR_IGEMM_SPLIT_COUNTERS int32 tile counters, ZERO before the first launch that sees them and left
+  int32_t* split_counters;/* optional: SR_IGEMM_SPLIT_COUNTERS int32 tile counters (align 4; nothing past them is touched), ZERO before the first launch that sees them and left
                              zero by every launch (one array per workspace: launches that may overlap in time need their own).  With
                              them a split-K launch finishes inside the GEMM kernel: a workgroup publishes its fp32 partial, counts
                              itself in, and the LAST of a tile's S workgroups to arrive sums the S partials in fixed z order and runs
@@ -166,9 +184,17 @@ int sr_layernorm_gather(const void* x, const int32_t* sel, int32_t nsel, int32_t
 /* Fused softmax(Q K^T / sqrt(d)) V (optimized_attention, attention.py:92-387), fp32 softmax statistics.
  *  q  [B, Tq, heads*d]   k [Bk, Tk, heads*d]   vt [Bk, heads, d, ldt] (V transposed, written by sr_igemm
  *  transpose_out)   o [B, Tq, heads*d].  Bk == B, or Bk == 1: every batch entry attends to the same K/V
- *  (OverlapCorresponder.pre_atten_inject, common_utils/stable_render_utils/corresponder.py:188-220). */
+ *  (OverlapCorresponder.pre_atten_inject, common_utils/stable_render_utils/corresponder.py:188-220).
+ * Extents: q is read up to (B*Tq - 1) * q_stride + heads*d elements, k up to (Bk*Tk - 1) * k_stride + heads*d, vt as
+ *  Bk*heads*d rows of ldt, and o written over (B*Tq - 1) * q_stride + heads*d (the row padding past heads*d is left alone).
+ * V^T padding: the kernels load whole 16-byte chunks of a V^T row up to ldt and multiply the columns [Tk, ldt) by a probability
+ *  of exactly 0, so those columns must hold FINITE values (any finite value: zeros, stale data); a NaN or an infinity there
+ *  turns the output NaN.  Nothing at or past column ldt of the last row is read.  Rows of q / k past heads*d are never read.
+ * Alignment (checked on the host: SR_ERR_INVALID before any launch): q, k and vt are fetched in 16-byte chunks -- the pointers
+ *  multiples of 16 bytes, d, q_stride, k_stride and ldt multiples of 8 (fp16) / 4 (fp32) elements; o is stored 4 elements at a
+ *  time -- a multiple of 8 bytes (fp16) / 16 bytes (fp32). */
 typedef struct {
-  const void* q; const void* k; const void* vt; void* o;
+  const void* q; const void* k; const void* vt; void* o;      /* align 16, 16, 16, 8 (fp16) / 16 (fp32) */
   int32_t B, Bk, Tq, Tk, heads, d, ldt, dtype;
   int32_t q_stride, k_stride;   /* row strides in elements (heads*d when packed) */
   float scale;                  /* d^-0.5 */
@@ -445,6 +471,9 @@ typedef struct {
                                                                Level of detail from the perspective-correct uv of the same triangle one
                                                                pixel right / down; fixed fp32 order = oracle/raster_ref.c tex_trilinear */
 } sr_draw;
+/* Planes are contiguous and exactly H*W pixels long; a pixel is read and written whole: color / normal_depth / noise as one 8-byte
+ * access (align 8), id as one 16-byte access (align 16), pos / canny / zbuf float by float (align 4).  Nothing outside the planes
+ * is touched, whatever W and H are against the 16 x 16 raster tile. */
 typedef struct {
   void* color;      /* [H,W,4] fp16 */
   int32_t* id;      /* [H,W,4] int32 */
@@ -466,7 +495,8 @@ int sr_gbuffer_depth_merge(const sr_gbuffer* acc, const sr_gbuffer* src, void* s
 int sr_defer_post(const void* color_rgba16f, const int32_t* ids, float* out_rgba, int32_t W, int32_t H, int32_t is_baking,
                   int32_t enable_gamma, int32_t enable_hdr, float gamma, float exposure, float saturation, float brightness,
                   float contrast, void* stream);
-/* scratch: see sr_raster_scratch_bytes(nt, W, H) */
+/* scratch: sr_raster_scratch_bytes(nt, W, H) bytes (per-triangle setup records followed by their int4 bounding boxes), align 16;
+ * contents need no initialisation and are dead after the call; fewer bytes are SR_ERR_INVALID, nothing past them is touched */
 int sr_raster_draw(const sr_draw* d, const sr_gbuffer* g, void* scratch, int64_t scratch_bytes, void* stream);
 int64_t sr_raster_scratch_bytes(int32_t nt, int32_t W, int32_t H);
 

@@ -3,7 +3,11 @@
  * MaskComposite, ImageColorToMask).  Same conventions as include/sr_hip.h, sr_tiled.h and sr_resample.h: caller-owned device
  * pointers to fp32, `stream` a hipStream_t, no allocation, no atomics and no synchronisation inside (every entry point can be captured
  * into a graph), 0 on success or a negative code with the text in sr_imgproc_last_error() (thread-local).  Strides are HOST arrays
- * of element strides.  A destination never aliases a source. */
+ * of element strides.  A destination never aliases a source.
+ * Alignment and extents: a pointer needs only the natural alignment of its element type (4 bytes for fp32 / int32, 8 for fp64 /
+ * int64); every access is one element wide.  Every tensor is
+ * exactly as long as its stated shape (a strided one ends at its last element) and nothing outside it is read or written;
+ * temporaries need no initialisation. */
 #ifndef SR_IMGPROC_H
 #define SR_IMGPROC_H
 #include <stdint.h>

@@ -2,7 +2,11 @@
  * torch.nn.functional.interpolate in five modes, bislerp (utils.py:335-409) and the 8-bit Lanczos of utils.py:411-416.  Same conventions
  * as include/sr_hip.h and include/sr_tiled.h: caller-owned device pointers, `stream` a hipStream_t, no allocation, no atomics and no
  * synchronisation inside (every entry point can be captured into a graph), 0 on success or a negative code with the text in
- * sr_resample_last_error() (thread-local). */
+ * sr_resample_last_error() (thread-local).
+ * Alignment and extents: a pointer needs only the natural alignment of its element type (1 byte for tmp_u8, 4 for fp32 / int32, 8 for
+ * fp64); 16-byte accesses are used only where the library finds the pointer and every row start 16-byte aligned.  Every tensor is
+ * exactly as long as its stated shape (a strided one ends at its last element) and nothing outside it is read or written;
+ * temporaries need no initialisation. */
 #ifndef SR_RESAMPLE_H
 #define SR_RESAMPLE_H
 #include <stdint.h>

@@ -2,7 +2,11 @@
  * (VAE.decode_tiled_ / VAE.encode_tiled_) = three passes of comfy.utils.tiled_scale (comfyUI/comfy/utils.py:448-475), averaged.
  * Helpers around the per-tile VAE launch plans of libsr_hip.so (include/sr_hip.h); same conventions: caller-owned device
  * pointers, `stream` a hipStream_t, no allocation or synchronisation inside, 0 on success or a negative code with the text in
- * sr_tiled_last_error() (thread-local). */
+ * sr_tiled_last_error() (thread-local).
+ * Alignment and extents: a pointer needs only the natural alignment of its element type (4 bytes for fp32 / int32, 8 for fp64 /
+ * int64); 16-byte accesses are used only where the library finds the pointer and every row start 16-byte aligned.  Every tensor is
+ * exactly as long as its stated shape (a strided one ends at its last element) and nothing outside it is read or written;
+ * temporaries need no initialisation. */
 #ifndef SR_TILED_H
 #define SR_TILED_H
 #include <stdint.h>

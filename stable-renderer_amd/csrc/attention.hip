@@ -1050,6 +1050,9 @@ extern "C" int sr_attention(const sr_attention_args* a, void* stream) {
   const int epc = a->dtype == SR_F16 ? 8 : 4;
   if (a->d % epc || a->q_stride % epc || a->k_stride % epc || a->ldt % epc || a->ldt < a->Tk)
     SR_FAIL(SR_ERR_INVALID, "sr_attention: d/strides must be multiples of %d and ldt >= Tk", epc);
+  const uintptr_t oal = a->dtype == SR_F16 ? 8 : 16;          // o: four elements per store; q / k / vt: 16-byte chunks (sr_hip.h)
+  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->vt) & 15 || ((uintptr_t)a->o & (oal - 1)))
+    SR_FAIL(SR_ERR_INVALID, "sr_attention: q / k / vt must be 16-byte aligned, o %d-byte", (int)oal);
   hipStream_t st = sr_stream(stream);
   const int d = a->d;
   if (a->dtype == SR_F16) {

@@ -1351,6 +1351,14 @@ static int igemm_check(const sr_igemm_args* a, int* M_, int* Ho_, int* Wo_) {
   else { Ho = a->H; Wo = a->W; }
   const int64_t M64 = (int64_t)a->B * Ho * Wo;
   if (M64 > 0x7fffffffLL / 2) SR_FAIL(SR_ERR_INVALID, "sr_igemm: M too large");
+  // alignment the kernels' vector accesses need (include/sr_hip.h); NULL passes
+  auto off = [](const void* p, uintptr_t al) { return ((uintptr_t)p & (al - 1)) != 0; };
+  if (off(a->a, 16) || off(a->a2, 16) || off(a->w, 16) || off(a->zero_page, 16) || off(a->bias, 16) || off(a->colsum, 16) ||
+      off(a->rowvec, 16) || off(a->residual, 16) || off(a->out, 16) || off(a->workspace, 16))
+    SR_FAIL(SR_ERR_INVALID, "sr_igemm: a / a2 / w / zero_page / bias / colsum / rowvec / residual / out / workspace must be 16-byte aligned");
+  if (off(a->row_stats, 8) || off(a->split_counters, 4) || off(a->prefetch, 4))
+    SR_FAIL(SR_ERR_INVALID, "sr_igemm: row_stats must be 8-byte, split_counters / prefetch 4-byte aligned");
+  if (a->rowvec && a->rowvec_ld % 4 && a->N % 4 == 0) SR_FAIL(SR_ERR_INVALID, "sr_igemm: rowvec_ld=%d must be a multiple of 4 floats", a->rowvec_ld);
   if (a->transpose_out && a->ldt < Ho * Wo) SR_FAIL(SR_ERR_INVALID, "sr_igemm: ldt < pixels per batch");
   *M_ = (int)M64; *Ho_ = Ho; *Wo_ = Wo;
   return SR_OK;

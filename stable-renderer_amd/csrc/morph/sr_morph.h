@@ -4,7 +4,11 @@
  * include/.  Conventions as in include/sr_imgproc.h: caller-owned device pointers to fp32, `stream` a hipStream_t, no allocation,
  * no atomics and no synchronisation inside (the entry points can be captured into a graph), 0 on success or a negative code with
  * the text in sr_morph_last_error() (thread-local).  No device pointer is dereferenced on the host and nothing is launched on bad
- * arguments. */
+ * arguments.
+ * Alignment and extents: a pointer needs only the natural alignment of its element type (4 bytes for fp32 / int32, 8 for fp64 /
+ * int64); 16-byte accesses are used only where the library finds the pointer and every row start 16-byte aligned.  Every tensor is
+ * exactly as long as its stated shape (a strided one ends at its last element) and nothing outside it is read or written;
+ * temporaries need no initialisation. */
 #ifndef SR_MORPH_H
 #define SR_MORPH_H
 #include <stdint.h>

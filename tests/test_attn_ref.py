@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 import attn_ref as R
 
-DISPATCH_HASH = "3a2ee0f5dad41e4d"   # sr_attention + launch_short: update route() / short_walk() with it
+DISPATCH_HASH = "e41dbe71b2aafa95"   # sr_attention + launch_short: update route() / short_walk() with it
 
 
 def sdpa(q, k, vt, heads, d, Tk, scale):
