@@ -17,7 +17,11 @@ PRIVATE_NODES is a third table of the same form as PRIVATE, for the private libr
 and Porter-Duff compositing).  It exists because the contents of the two older tables are pinned by tests; names() lists all three.
 
 PRIVATE_MODELS is a fourth table of the same form, for the private libraries that run a whole model (libsr_esrgan.so: the upscale
-models).  names() and the three older tables are pinned by tests, so all_names() = names() + this table is what builds everything.
+models).  names() and the three older tables are pinned by tests, so all_names() = names() + this table.
+
+PRIVATE_EXTRA is the fifth table of the same form and the open-ended one: all_names() and the four older tables are pinned by tests,
+so every later private library joins this table (libsr_canny.so is the first), and no test pins its length or its full content.
+every_name() = all_names() + this table is what builds everything.
 
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
 import hashlib
@@ -47,6 +51,10 @@ PRIVATE_NODES = {
 PRIVATE_MODELS = {
     "esrgan": ("esrgan", "esrgan.hip", "sr_esrgan.h", "SR_ESRGAN_SRC_HASH"),
 }
+# name -> (directory, source, private header next to the source, hash macro); later private libraries join this table
+PRIVATE_EXTRA = {
+    "canny": ("canny", "canny.hip", "sr_canny.h", "SR_CANNY_SRC_HASH"),
+}
 
 
 def names():
@@ -55,8 +63,13 @@ def names():
 
 
 def all_names():
-    """names() and the model libraries of PRIVATE_MODELS: everything sidelib builds"""
+    """names() and the model libraries of PRIVATE_MODELS"""
     return names() + list(PRIVATE_MODELS)
+
+
+def every_name():
+    """all_names() and the libraries of PRIVATE_EXTRA: everything sidelib builds"""
+    return all_names() + list(PRIVATE_EXTRA)
 
 
 def entry(name):
@@ -64,7 +77,7 @@ def entry(name):
     if name in REGISTRY:
         d, src, hdr, macro = REGISTRY[name]
         return d, src, os.path.join(HERE, "..", "..", "include", hdr), macro
-    for table in (PRIVATE, PRIVATE_NODES, PRIVATE_MODELS):
+    for table in (PRIVATE, PRIVATE_NODES, PRIVATE_MODELS, PRIVATE_EXTRA):
         if name in table:
             d, src, hdr, macro = table[name]
             break
@@ -119,5 +132,5 @@ def build(name, force=False):
 
 
 if __name__ == "__main__":
-    for n in [a for a in sys.argv[1:] if a != "--force"] or all_names():
+    for n in [a for a in sys.argv[1:] if a != "--force"] or every_name():
         print(build(n, force="--force" in sys.argv))

@@ -3,7 +3,8 @@ engine/managers/diffusionManager.py:160-259, call site renderManager.py:966-988)
 colour / normal / canny as RGBA8 PNG (value*255 truncated, alpha 255 added to 3-channel maps, 1- or 2-D maps repeated to
 grey), id / pos / noise as raw ``.npy``, depth min-max normalised over its positive values with alpha = depth > 0.
 Dumps written here load with the reference's ``IDSequenceLoader`` / ``NoiseSequenceLoader`` / ``ImageSequenceLoader`` and vice
-versa (``nodes.py`` has the loader mirrors).  Host-side file I/O only (numpy + PIL): the planes come off the device once."""
+versa (``nodes.py`` has the loader mirrors).  Host-side file I/O only (numpy + PIL): the planes come off the device once.  ``output_ai_canny`` is the exception: it is the
+reference's _outputAICannyMap (diffusionManager.py:261-285), whose cv2.Canny runs on the device here."""
 import os
 
 import numpy as np
@@ -46,6 +47,18 @@ class GBufferDump:
         alpha = (dn > 0).astype(np.uint8) * 255
         fn = f"depth_{frame_num}.png" if frame_num is not None else "depth.png"
         Image.fromarray(np.stack([gray, gray, gray, alpha], axis=-1), "RGBA").save(os.path.join(self._dir("depth"), fn))
+
+    def output_ai_canny(self, color, frame_num=None):
+        """DiffusionManager._outputAICannyMap (diffusionManager.py:261-278): cv2.Canny((color * 255).astype(uint8), 100, 200) of the
+        colour map -- a device tensor (H,W,C), float in [0,1] or uint8; the detector runs on the GPU (canny.cv_canny) -- written
+        as ``ai_canny/ai_canny_<frame>.png``, single-channel 8-bit as cv2.imwrite writes a 2-D uint8 array.  Not the shader's canny
+        plane, which dump_gbuffer writes."""
+        from . import canny as CN
+        if color.dim() != 3:
+            raise ValueError(f"output_ai_canny: one colour map (H,W,C) is required, got shape {tuple(color.shape)}")
+        edges = CN.cv_canny(color, 100, 200).cpu().numpy()
+        fn = f"ai_canny_{frame_num}.png" if frame_num is not None else "ai_canny.png"
+        Image.fromarray(edges, "L").save(os.path.join(self._dir("ai_canny"), fn))
 
     def dump_gbuffer(self, gbuf, frame_num):
         """one frame of ``scene.GBuffer`` planes, as RenderManager does when ShouldOutputFrame (renderManager.py:966-988)"""

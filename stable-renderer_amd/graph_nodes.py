@@ -879,6 +879,26 @@ MORPH_NODES = {"Morphology": Morphology, "PorterDuffImageComposite": PorterDuffI
                "JoinImageWithAlpha": JoinImageWithAlpha}
 
 
+# ---- the Canny preprocessor (comfy_extras/nodes_canny.py) over canny.py ----------------------------------------------------------
+class Canny:
+    """nodes_canny.py:11-27: kornia's canny(...)[1] repeated to three channels, as canny.py states it"""
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "detect_edge"
+    CATEGORY = "image/preprocessors"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE",), "low_threshold": ("FLOAT", {"default": 0.4, "min": 0.01, "max": 0.99, "step": 0.01}),
+                             "high_threshold": ("FLOAT", {"default": 0.8, "min": 0.01, "max": 0.99, "step": 0.01})}}
+
+    def detect_edge(self, image, low_threshold, high_threshold):
+        from . import canny as CN
+        return (CN.canny(_dev(image), low_threshold, high_threshold),)
+
+
+CANNY_NODES = {"Canny": Canny}
+
+
 # ---- upscale models (comfy_extras/nodes_upscale_model.py) over esrgan.py ---------------------------------------------------------
 class UpscaleModelLoader:
     """nodes_upscale_model.py:8-24 -> (UPSCALE_MODEL,): a registered state dict or a file under $SR_MODELS_DIR/upscale_models/"""
@@ -1005,6 +1025,9 @@ for _name, _cls in IMGPROC_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in MORPH_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in CANNY_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in UPSCALE_NODES.items():

@@ -223,7 +223,7 @@ class FramePipeline:
         overlap step, the injected frame's tokens are broadcast per transformer block and decoded frames go to rank 0 for
         the ordered corr-map update.  Without it the pipeline is a self-contained replica."""
         self.unet, self.vae, self.scene = unet, vae, scene
-        # controls: [("depth" | "normal" | "color" | "canny", ControlNet)] -- ControlNets driven by the G-buffer planes of the
+        # controls: [("depth" | "normal" | "color" | "canny" | "ai_canny", ControlNet)] -- ControlNets driven by the G-buffer planes of the
         # same views, as the reference's miku-control workflow (depth + normalbae; EngineData.depth_maps / normal_maps ->
         # ControlNetApply)
         self.controls = list(controls or [])
@@ -257,6 +257,8 @@ class FramePipeline:
         self.keep_planes = bool(keep_planes or self.controls)
         self.normal_depth = torch.zeros(n_views, self.H, self.W, 4, dtype=torch.float16, device=dev) if self.keep_planes else None
         self.canny = torch.zeros(n_views, self.H, self.W, 3, dtype=torch.float32, device=dev) if self.keep_planes else None
+        # the colour map's alpha, kept only for the "ai_canny" hint (1 - masks would round it a second time)
+        self.alphas = torch.zeros(n_views, self.H, self.W, dtype=torch.float16, device=dev) if any(k == "ai_canny" for k, _ in self.controls) else None
         self.frame0 = 0
 
     def set_prompt(self, positive, negative):
@@ -294,6 +296,8 @@ class FramePipeline:
             self.colors[i].copy_(self.gbuf.color[..., :3])
             alpha = self.gbuf.color[..., 3].contiguous()
             self.masks[i].copy_(1.0 - alpha)
+            if self.alphas is not None:
+                self.alphas[i].copy_(alpha)
             if self.keep_planes:
                 self.normal_depth[i].copy_(self.gbuf.normal_depth)
                 self.canny[i].copy_(self.gbuf.canny)
@@ -349,10 +353,17 @@ class FramePipeline:
         return samples
 
     def control_hints(self):
-        """the G-buffer planes of the rendered views as ControlNet hints, one (N,3,H,W) tensor per attached net"""
+        """the G-buffer planes of the rendered views as ControlNet hints, one (N,3,H,W) tensor per attached net.  "canny" is the
+        shader's plane; "ai_canny" is what the reference's outputAICannyMap makes of the colour map (cv2.Canny at 100 / 200 of the
+        RGBA colour), as 0 / 1 on three channels"""
         planes = {"depth": lambda: self.normal_depth[..., 3:4].expand(-1, -1, -1, 3), "normal": lambda: self.normal_depth[..., :3],
-                  "color": lambda: self.colors, "canny": lambda: self.canny}
+                  "color": lambda: self.colors, "canny": lambda: self.canny, "ai_canny": self._ai_canny}
         return [planes[k]().permute(0, 3, 1, 2).float().contiguous() for k, _ in self.controls]
+
+    def _ai_canny(self):
+        from . import canny as CN
+        rgba = torch.cat((self.colors, self.alphas.unsqueeze(-1)), dim=-1)             # the G-buffer's fp16 RGBA colour again
+        return (CN.cv_canny(rgba, 100, 200) > 0).unsqueeze(-1).expand(-1, -1, -1, 3)
 
     def decode(self, samples):
         self.vplan["z"].copy_(samples)
