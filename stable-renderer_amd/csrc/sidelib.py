@@ -20,7 +20,8 @@ PRIVATE_MODELS is a fourth table of the same form, for the private libraries tha
 models).  names() and the three older tables are pinned by tests, so all_names() = names() + this table.
 
 PRIVATE_EXTRA is the fifth table of the same form and the open-ended one: all_names() and the four older tables are pinned by tests,
-so every later private library joins this table (libsr_canny.so is the first), and no test pins its length or its full content.
+so every later private library joins this table (libsr_canny.so is the first, libsr_taesd.so, the TAESD tiny autoencoder, the
+second), and no test pins its length or its full content.
 every_name() = all_names() + this table is what builds everything.
 
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
@@ -54,6 +55,7 @@ PRIVATE_MODELS = {
 # name -> (directory, source, private header next to the source, hash macro); later private libraries join this table
 PRIVATE_EXTRA = {
     "canny": ("canny", "canny.hip", "sr_canny.h", "SR_CANNY_SRC_HASH"),
+    "taesd": ("taesd", "taesd.hip", "sr_taesd.h", "SR_TAESD_SRC_HASH"),
 }
 
 

@@ -933,6 +933,68 @@ class ImageUpscaleWithModel:
 UPSCALE_NODES = {"UpscaleModelLoader": UpscaleModelLoader, "ImageUpscaleWithModel": ImageUpscaleWithModel}
 
 
+# ---- stand-alone VAEs (comfyUI/nodes.py:702-769) over vae.py and taesd.py ----------------------------------------------------------
+class VAELoader:
+    """nodes.py:702-769 -> (VAE,).  ``taesd`` / ``taesdxl``: the first ``vae_approx`` names that start with ``<name>_encoder.`` and
+    ``<name>_decoder.`` (registered providers, then files under $SR_MODELS_DIR/vae_approx/), merged under the prefixes
+    ``taesd_encoder.`` / ``taesd_decoder.`` with the model family's vae_scale (load_taesd).  Any other name: a ``vae`` file, which
+    becomes the VAEDecoder (+ VAEEncoder) that CheckpointLoaderSimple builds from a checkpoint's VAE keys, or a TAESD where the
+    file carries ``taesd_decoder.1.weight`` (comfy/sd.py:227-228)."""
+    RETURN_TYPES = ("VAE",)
+    FUNCTION = "load_vae"
+    CATEGORY = "loaders"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"vae_name": ("STRING", {})}}
+
+    @staticmethod
+    def vae_list():
+        """nodes.py:703-725: the vae names, plus taesd / taesdxl where both halves are there"""
+        vaes, approx = WT.names("vae"), WT.names("vae_approx")
+        for name in ("taesd", "taesdxl"):
+            if any(v.startswith(name + "_decoder.") for v in approx) and any(v.startswith(name + "_encoder.") for v in approx):
+                vaes.append(name)
+        return vaes
+
+    @staticmethod
+    def load_taesd(name):
+        """nodes.py:727-747; a missing half is a FileNotFoundError (the reference's next() raises StopIteration)"""
+        from . import taesd as TA
+        approx = WT.names("vae_approx")
+        sd = {}
+        for half in ("encoder", "decoder"):
+            fn = next((a for a in approx if a.startswith(f"{name}_{half}.")), None)
+            if fn is None:
+                raise FileNotFoundError(f"vae_approx '{name}_{half}.*' is neither registered (stable_renderer_amd.weights.register_vae_approx) "
+                                        f"nor a file under $SR_MODELS_DIR/vae_approx/")
+            for k, v in WT.resolve("vae_approx", fn).items():
+                sd[f"taesd_{half}.{k}"] = v
+        sd["vae_scale"] = torch.tensor(TA.SD_SCALE if name == "taesd" else TA.SDXL_SCALE)
+        return sd
+
+    def load_vae(self, vae_name):
+        sd = self.load_taesd(vae_name) if vae_name in ("taesd", "taesdxl") else WT.resolve("vae", vae_name)
+        if "decoder.up_blocks.0.resnets.0.norm1.weight" in sd:
+            raise NotImplementedError(f"VAELoader: '{vae_name}' is a diffusers-format VAE (decoder.up_blocks.* keys); only the "
+                                      "ldm layout (decoder.up.N.block.*) loads here")
+        if "taesd_decoder.1.weight" in sd:
+            from . import taesd as TA
+            return (TA.TAESD(sd),)                       # the kernel is fp16 with fp32 accumulation whatever SR_DTYPE says
+        if "decoder.conv_in.weight" not in sd:
+            raise NotImplementedError(f"VAELoader: '{vae_name}' holds neither decoder.conv_in.weight nor taesd_decoder.1.weight: "
+                                      "not an AutoencoderKL or TAESD state dict")
+        from .vae import VAEDecoder, VAEEncoder
+        dt = _dtype()
+        vae = VAEDecoder(sd, dtype=dt, prefix="decoder.")
+        if "encoder.conv_in.weight" in sd:
+            vae = VAE(vae, VAEEncoder(sd, dtype=dt, prefix="encoder."))
+        return (vae,)
+
+
+VAE_NODES = {"VAELoader": VAELoader}
+
+
 class LoadImage:
     """comfyUI/nodes.py:1623-1665 -> (IMAGE (1,H,W,3) in [0,1], MASK = 1 - alpha or 64x64 zeros).  ``image`` is a path, or a name
     under $SR_INPUT_DIR (the reference's input directory)"""
@@ -1031,6 +1093,9 @@ for _name, _cls in CANNY_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in UPSCALE_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in VAE_NODES.items():
     register_node(_name, _cls)
 
 

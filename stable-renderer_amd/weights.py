@@ -3,13 +3,13 @@ comfyUI/nodes.py:554-573, 689-700, 770-783) and the LoRA merge they need.
 
 There is no network and no checkpoint in this image, so names resolve in this order: (1) a provider registered in-process
 (``register_checkpoint`` ...: tests and bench register seeded synthetic weights of the exact SD1.5 shapes), (2) a
-``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras,upscale_models}/<name>`` (the reference's folder_paths layout),
-else FileNotFoundError.  Nothing here touches the GPU; tensors stay on the host until UNet / VAEDecoder pack them."""
+``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras,upscale_models,vae,vae_approx}/<name>`` (the reference's
+folder_paths layout), else FileNotFoundError.  Nothing here touches the GPU; tensors stay on the host until UNet / VAEDecoder pack them."""
 import os
 
 import torch
 
-_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}, "upscale_models": {}}
+_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}, "upscale_models": {}, "vae": {}, "vae_approx": {}}
 
 
 def _norm(name):
@@ -34,6 +34,27 @@ def register_lora(name, provider):
 def register_upscale_model(name, provider):
     """provider() -> the state dict of an upscale model (UpscaleModelLoader, comfy_extras/nodes_upscale_model.py:18-24)"""
     _REG["upscale_models"][_norm(name)] = provider
+
+
+def register_vae(name, provider):
+    """provider() -> the state dict of a stand-alone VAE file (VAELoader, comfyUI/nodes.py:758-769)"""
+    _REG["vae"][_norm(name)] = provider
+
+
+def register_vae_approx(name, provider):
+    """provider() -> the state dict of one half of a TAESD (``taesd_decoder.pth`` ...: VAELoader.load_taesd, nodes.py:727-747)"""
+    _REG["vae_approx"][_norm(name)] = provider
+
+
+def names(kind):
+    """what the reference's folder_paths.get_filename_list(kind) lists: the registered names, then the files of
+    $SR_MODELS_DIR/<kind>/ (sorted, top level)"""
+    out = list(_REG[kind])
+    root = os.environ.get("SR_MODELS_DIR")
+    d = os.path.join(root, kind) if root else None
+    if d and os.path.isdir(d):
+        out += [f for f in sorted(os.listdir(d)) if os.path.isfile(os.path.join(d, f)) and f not in out]
+    return out
 
 
 def clear_registry():
