@@ -209,9 +209,10 @@ def ratio(got, ref, bound, out=None):
 
 
 def _in(x):
-    """the exact value of an fp32 / fp16 kernel input"""
+    """the exact value of an fp32 / fp16 kernel input (or of a float64 one: tests/plan_ref.py chains whole plans in float64 and
+    feeds every reference the float64 result of the op before it)"""
     x = np.asarray(x)
-    assert x.dtype in (np.dtype(f32), np.dtype(f16)), x.dtype
+    assert x.dtype in (np.dtype(f32), np.dtype(f16), np.dtype(f64)), x.dtype
     return x.astype(f64)
 
 
