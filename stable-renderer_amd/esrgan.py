@@ -346,9 +346,15 @@ class UpscaleModel:
 
 
 def load_upscale_model(state_dict):
-    """UpscaleModelLoader.load_model on a state dict (nodes_upscale_model.py:20-24): strips ``module.`` where the reference does"""
+    """UpscaleModelLoader.load_model on a state dict (nodes_upscale_model.py:20-24): strips ``module.`` where the reference does.
+    The reference's first test (model_loading.py:37-39) sends a file with body.0.weight and body.1.weight to SRVGGNetCompact:
+    compact.CompactUpscaleModel here; everything else is UpscaleModel's to run or to refuse by name"""
     if "module.layers.0.residual_group.blocks.0.norm1.weight" in state_dict:
         state_dict = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+    keys = unwrap(state_dict).keys()
+    if "body.0.weight" in keys and "body.1.weight" in keys:
+        from .compact import CompactUpscaleModel
+        return CompactUpscaleModel(state_dict)
     return UpscaleModel(state_dict)
 
 
