@@ -167,6 +167,11 @@ class CheckpointLoaderSimple:
             from .unet import SDXL_CFG
             cfg = dict(SDXL_CFG if "label_emb.0.0.weight" in unet_sd else SD15_CFG)   # (model_detection.py: SDXL carries label_emb)
             clip = None
+            from . import clip as CL
+            if output_clip and CL.has_text_encoder(r):
+                # lazy: the keys are sorted, the weights packed and the tokenizer looked up at the first tokenize / encode_from_tokens
+                te = {k: v for k, v in r.items() if k.startswith(CL.CKPT_PREFIXES)}
+                clip = CL.CLIP(lambda: CL.clip_from_state_dicts(CL.checkpoint_text_encoders(te))._get(), name=str(ckpt_name))
             vae = VAEDecoder(vae_sd, dtype=dt, prefix="decoder.") if output_vae else None
             if vae is not None and "encoder.conv_in.weight" in vae_sd:
                 from .vae import VAEEncoder
@@ -933,6 +938,106 @@ class ImageUpscaleWithModel:
 UPSCALE_NODES = {"UpscaleModelLoader": UpscaleModelLoader, "ImageUpscaleWithModel": ImageUpscaleWithModel}
 
 
+# ---- text encoders (comfyUI/nodes.py:617-631, 913-947, comfy_extras/nodes_clip_sdxl.py) over clip.py ------------------------------------
+class CLIPSetLastLayer:
+    """nodes.py:617-631"""
+    RETURN_TYPES = ("CLIP",)
+    FUNCTION = "set_last_layer"
+    CATEGORY = "conditioning"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"clip": ("CLIP",), "stop_at_clip_layer": ("INT", {"default": -1, "min": -24, "max": -1, "step": 1})}}
+
+    def set_last_layer(self, clip, stop_at_clip_layer):
+        clip = clip.clone()
+        clip.clip_layer(stop_at_clip_layer)
+        return (clip,)
+
+
+class CLIPLoader:
+    """nodes.py:913-931 -> (CLIP,): a registered state dict or a file under $SR_MODELS_DIR/clip/"""
+    RETURN_TYPES = ("CLIP",)
+    FUNCTION = "load_clip"
+    CATEGORY = "advanced/loaders"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"clip_name": ("STRING", {}), "type": (["stable_diffusion", "stable_cascade"],)}}
+
+    def load_clip(self, clip_name, type="stable_diffusion"):
+        from . import clip as CL
+        return (CL.load_clip([WT.resolve("clip", clip_name)], name=str(clip_name), clip_type=type),)
+
+
+class DualCLIPLoader:
+    """nodes.py:933-947 -> (CLIP,): clip-l and clip-g, in either order"""
+    RETURN_TYPES = ("CLIP",)
+    FUNCTION = "load_clip"
+    CATEGORY = "advanced/loaders"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"clip_name1": ("STRING", {}), "clip_name2": ("STRING", {})}}
+
+    def load_clip(self, clip_name1, clip_name2):
+        from . import clip as CL
+        return (CL.load_clip([WT.resolve("clip", clip_name1), WT.resolve("clip", clip_name2)], name=f"{clip_name1}+{clip_name2}"),)
+
+
+class CLIPTextEncodeSDXLRefiner:
+    """nodes_clip_sdxl.py:4-21"""
+    RETURN_TYPES = ("CONDITIONING",)
+    FUNCTION = "encode"
+    CATEGORY = "advanced/conditioning"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"ascore": ("FLOAT", {"default": 6.0, "min": 0.0, "max": 1000.0, "step": 0.01}),
+                             "width": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "height": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "text": ("STRING", {"multiline": True}), "clip": ("CLIP",)}}
+
+    def encode(self, clip, ascore, width, height, text):
+        cond, pooled = clip.encode_from_tokens(clip.tokenize(text), return_pooled=True)
+        return ([[cond, {"pooled_output": pooled, "aesthetic_score": ascore, "width": width, "height": height}]],)
+
+
+class CLIPTextEncodeSDXL:
+    """nodes_clip_sdxl.py:23-51: text_g and text_l tokenized apart, the shorter padded with sections of the empty prompt"""
+    RETURN_TYPES = ("CONDITIONING",)
+    FUNCTION = "encode"
+    CATEGORY = "advanced/conditioning"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"width": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "height": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "crop_w": ("INT", {"default": 0, "min": 0, "max": MAX_RESOLUTION}),
+                             "crop_h": ("INT", {"default": 0, "min": 0, "max": MAX_RESOLUTION}),
+                             "target_width": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "target_height": ("INT", {"default": 1024.0, "min": 0, "max": MAX_RESOLUTION}),
+                             "text_g": ("STRING", {"multiline": True, "default": "CLIP_G"}), "clip": ("CLIP",),
+                             "text_l": ("STRING", {"multiline": True, "default": "CLIP_L"})}}
+
+    def encode(self, clip, width, height, crop_w, crop_h, target_width, target_height, text_g, text_l):
+        tokens = clip.tokenize(text_g)
+        tokens["l"] = clip.tokenize(text_l)["l"]
+        if len(tokens["l"]) != len(tokens["g"]):
+            empty = clip.tokenize("")
+            while len(tokens["l"]) < len(tokens["g"]):
+                tokens["l"] += empty["l"]
+            while len(tokens["l"]) > len(tokens["g"]):
+                tokens["g"] += empty["g"]
+        cond, pooled = clip.encode_from_tokens(tokens, return_pooled=True)
+        return ([[cond, {"pooled_output": pooled, "width": width, "height": height, "crop_w": crop_w, "crop_h": crop_h,
+                         "target_width": target_width, "target_height": target_height}]],)
+
+
+CLIP_NODES = {"CLIPSetLastLayer": CLIPSetLastLayer, "CLIPLoader": CLIPLoader, "DualCLIPLoader": DualCLIPLoader,
+              "CLIPTextEncodeSDXL": CLIPTextEncodeSDXL, "CLIPTextEncodeSDXLRefiner": CLIPTextEncodeSDXLRefiner}
+
+
 # ---- stand-alone VAEs (comfyUI/nodes.py:702-769) over vae.py and taesd.py ----------------------------------------------------------
 class VAELoader:
     """nodes.py:702-769 -> (VAE,).  ``taesd`` / ``taesdxl``: the first ``vae_approx`` names that start with ``<name>_encoder.`` and
@@ -1096,6 +1201,9 @@ for _name, _cls in UPSCALE_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in VAE_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in CLIP_NODES.items():
     register_node(_name, _cls)
 
 

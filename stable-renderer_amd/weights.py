@@ -3,13 +3,15 @@ comfyUI/nodes.py:554-573, 689-700, 770-783) and the LoRA merge they need.
 
 There is no network and no checkpoint in this image, so names resolve in this order: (1) a provider registered in-process
 (``register_checkpoint`` ...: tests and bench register seeded synthetic weights of the exact SD1.5 shapes), (2) a
-``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras,upscale_models,vae,vae_approx}/<name>`` (the reference's
-folder_paths layout), else FileNotFoundError.  Nothing here touches the GPU; tensors stay on the host until UNet / VAEDecoder pack them."""
+``.safetensors`` file under ``$SR_MODELS_DIR/{checkpoints,controlnet,loras,upscale_models,vae,vae_approx,clip,embeddings}/<name>`` (the
+reference's folder_paths layout), else FileNotFoundError.  The CLIP tokenizer's ``merges.txt`` is a model resource of the same kind:
+``register_tokenizer(path)``, else ``$SR_MODELS_DIR/tokenizer/merges.txt``.  Nothing here touches the GPU; tensors stay on the host until UNet / VAEDecoder pack them."""
 import os
 
 import torch
 
-_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}, "upscale_models": {}, "vae": {}, "vae_approx": {}}
+_REG = {"checkpoints": {}, "controlnet": {}, "loras": {}, "upscale_models": {}, "vae": {}, "vae_approx": {}, "clip": {}, "embeddings": {}}
+_TOKENIZER = {"path": None}
 
 
 def _norm(name):
@@ -46,6 +48,37 @@ def register_vae_approx(name, provider):
     _REG["vae_approx"][_norm(name)] = provider
 
 
+def register_clip(name, provider):
+    """provider() -> the state dict of a stand-alone text-encoder file (CLIPLoader / DualCLIPLoader, comfyUI/nodes.py:913-947)"""
+    _REG["clip"][_norm(name)] = provider
+
+
+def register_embedding(name, provider):
+    """provider() -> what a textual-inversion file holds (``embedding:<name>`` in a prompt; clip_tokenizer.load_embed reads it)"""
+    _REG["embeddings"][_norm(name)] = provider
+
+
+def register_tokenizer(path):
+    """the CLIP tokenizer's merges.txt (or the directory that holds it); None forgets it"""
+    _TOKENIZER["path"] = None if path is None else str(path)
+
+
+def tokenizer_merges():
+    """-> the path of merges.txt: the registered one, else $SR_MODELS_DIR/tokenizer/merges.txt; FileNotFoundError names both places"""
+    cands = []
+    p = _TOKENIZER["path"]
+    if p is not None:
+        cands.append(os.path.join(p, "merges.txt") if os.path.isdir(p) else p)
+    root = os.environ.get("SR_MODELS_DIR")
+    if root:
+        cands.append(os.path.join(root, "tokenizer", "merges.txt"))
+    for c in cands:
+        if os.path.isfile(c):
+            return c
+    raise FileNotFoundError("the CLIP tokenizer needs its merges.txt: it is neither registered (stable_renderer_amd.weights."
+                            "register_tokenizer(path)) nor a file at $SR_MODELS_DIR/tokenizer/merges.txt")
+
+
 def names(kind):
     """what the reference's folder_paths.get_filename_list(kind) lists: the registered names, then the files of
     $SR_MODELS_DIR/<kind>/ (sorted, top level)"""
@@ -60,6 +93,7 @@ def names(kind):
 def clear_registry():
     for d in _REG.values():
         d.clear()
+    _TOKENIZER["path"] = None
 
 
 def _file(kind, name):
