@@ -220,7 +220,18 @@ class ControlNetLoader:
     def load_controlnet(self, control_net_name):
         from .controlnet import ControlNet
         r = WT.resolve("controlnet", control_net_name)
-        if "state_dict" in r and isinstance(r["state_dict"], dict):
+        wrapped = "state_dict" in r and isinstance(r["state_dict"], dict)
+        sd = r["state_dict"] if wrapped else r
+        if "control_model.zero_convs.0.0.weight" not in sd and "zero_convs.0.0.weight" not in sd:
+            # load_controlnet falls through to load_t2i_adapter (comfy/controlnet.py:420-428): a file without zero convs is adapter data
+            # or nothing.  _dtype() is not passed on: the adapter network always runs in fp16 (its kernel has no other form), and the
+            # control buffers it emits take the dtype of the UNet plan they are built for
+            from . import t2i_adapter as TA
+            net = TA.load_t2i_adapter(sd)
+            if net is None:
+                raise ValueError(f"ControlNetLoader: {control_net_name!r} {TA.NOT_CONTROL}")
+            return (net,)
+        if wrapped:
             return (ControlNet(r["state_dict"], r.get("cfg"), dtype=_dtype()),)
         sd = {(k[len("control_model."):] if k.startswith("control_model.") else k): v for k, v in r.items()}
         return (ControlNet(sd, None, dtype=_dtype()),)

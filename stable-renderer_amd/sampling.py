@@ -223,25 +223,35 @@ class DiffusionRunner:
         pb = PlanBuilder(self.unet.device, self.unet.dtype)
         inputs = (pb.buf(B, cfgu["in_channels"], h, w, dtype=torch.float32, zero=True),
                   pb.buf(B, dtype=torch.float32, zero=True), pb.buf(B, n_ctx, cfgu["context_dim"], zero=True))
-        cps = [c.build(B, h, w, *inputs, n_ctx=n_ctx) for c in self.controlnets]
-        outs, mid = list(cps[0]["output"]), cps[0]["middle"]
-        for cp in cps[1:]:                          # control_merge: element-wise sums of the residual lists
+        cps = []
+        for c in self.controlnets:
+            if getattr(c, "is_t2i_adapter", False):
+                # a T2I-Adapter reads only its hint: no step plan, its feature maps are emitted into control buffers once per hint
+                if self.shard is not None and self.shard.active:
+                    raise NotImplementedError("a T2I-Adapter on an active ViewShard is not supported")
+                if (h, w) != (self.h, self.w):
+                    raise NotImplementedError("a T2I-Adapter with area-cropped conditioning is not supported")
+                cps.append(c.build(B, h, w, *inputs, n_ctx=n_ctx, n_hints=self.N, unet_cfg=cfgu, out_dtype=self.unet.dtype))
+            else:
+                cps.append(c.build(B, h, w, *inputs, n_ctx=n_ctx))
+
+        def merge(xs, ys):                          # control_merge: element-wise sums of the lists, None passes through
+            xs, ys = list(xs or []), list(ys or [])
             merged = []
-            for a, b in zip(outs, cp["output"]):
+            for i in range(max(len(xs), len(ys))):
+                a, b = xs[i] if i < len(xs) else None, ys[i] if i < len(ys) else None
                 if a is None or b is None:
                     merged.append(a if b is None else b)
                 else:
                     y = pb.buf(*a.shape)
                     pb.add(a, b, y)
                     merged.append(y)
-            outs = merged
-            if mid is not None and cp["middle"] is not None:
-                m2 = pb.buf(*mid.shape)
-                pb.add(mid, cp["middle"], m2)
-                mid = m2
-            elif mid is None:
-                mid = cp["middle"]
-        return dict(output=outs, middle=mid), inputs, dict(plans=cps, merge=pb.take())
+            return merged
+        outs, ins, mid = list(cps[0]["output"] or []), list(cps[0].get("input") or []), cps[0]["middle"]
+        for cp in cps[1:]:
+            outs, ins = merge(outs, cp["output"]), merge(ins, cp.get("input"))
+            mid = merge([mid], [cp["middle"]])[0]
+        return dict(output=outs or None, middle=mid, input=ins), inputs, dict(plans=cps, merge=pb.take())
 
     def _run_controls(self, p, sigma):
         """the ControlNet encoders of one model call, then the plan that sums their residuals.  A net outside its sigma window
@@ -254,6 +264,14 @@ class DiffusionRunner:
             active = True
             if (lo, hi) != (0.0, 1.0):
                 active = not (sigma > CD.percent_to_sigma(self.ms, lo) or sigma < CD.percent_to_sigma(self.ms, hi))
+            if "run" in cp:                                 # a T2I-Adapter: evaluated when the hints were loaded, nothing runs per step
+                if active and cp.get("_zeroed"):
+                    cp["emit"]()                            # back inside its window: the cached maps again
+                    cp["_zeroed"] = False
+                elif not active and not cp.get("_zeroed"):
+                    cp["zero"]()
+                    cp["_zeroed"] = True
+                continue
             if active:
                 cp["step"].run()
                 cp["_zeroed"] = False
@@ -266,11 +284,26 @@ class DiffusionRunner:
 
     def set_control_hints(self, hints):
         """hints: one (N,3,8h,8w) tensor in [0,1] per ControlNet (ControlNetApply's image.movedim(-1,1), nodes.py:745-760);
-        the same hint serves the cond and uncond halves of the batch"""
+        the same hint serves the cond and uncond halves of the batch.  A T2I-Adapter in the list is evaluated on its hint when the
+        next run loads it, and not again until this is called with another hint"""
         if len(hints) != len(self.controlnets):
             raise ValueError(f"{len(self.controlnets)} ControlNets need as many hints, got {len(hints)}")
         self._hints = list(hints)
         self._hints_loaded = False
+
+    @staticmethod
+    def _load_adapter_hint(cp, hint):
+        """a T2I-Adapter's plan: the network runs once per hint -- again only when set_control_hints() brought another tensor, or the
+        same one written to since -- and its maps stay cached in the plan; a run that starts afresh gets them emitted again if the
+        previous one left the adapter's window"""
+        # (an inference-mode tensor has no version counter -- and cannot be written to in place outside inference mode)
+        key = (id(hint), None if hint.is_inference() else hint._version, tuple(hint.shape))
+        if cp.get("_hint_key") != key or cp.get("_hint_ref") is not hint:
+            cp["run"](hint)
+            cp["_hint_key"], cp["_hint_ref"], cp["_zeroed"] = key, hint, False
+        elif cp.get("_zeroed"):
+            cp["emit"]()
+            cp["_zeroed"] = False
 
     def set_vector_conditioning(self, y_positive, y_negative=None):
         """SDXL-family ``y`` (pooled text + size / crop embeddings, (1 | N, adm_in_channels)); the negative half defaults to the
@@ -399,6 +432,9 @@ class DiffusionRunner:
                 if self._hints is None:
                     raise ValueError("ControlNets are attached: call set_control_hints() before sampling")
                 for cp, hint in zip(p["cn"]["plans"], self._hints):
+                    if "run" in cp:
+                        self._load_adapter_hint(cp, hint)
+                        continue
                     hv = hint.to(cp["hint"].device, torch.float32)
                     th, tw = cp["hint"].shape[2], cp["hint"].shape[3]
                     if (hv.shape[2], hv.shape[3]) != (th, tw):
@@ -461,6 +497,9 @@ class DiffusionRunner:
             if self._hints is None:
                 raise ValueError("ControlNets are attached: call set_control_hints() before sampling")
             for cp, hint in zip(p["cn"]["plans"], self._hints):
+                if "run" in cp:
+                    self._load_adapter_hint(cp, hint)
+                    continue
                 hb = cp["hint"]
                 hv = hint.to(hb.device, torch.float32)
                 for c in range(self.copies):

@@ -324,7 +324,8 @@ class UNet:
         None.  The indices live in a device tensor read at run time, so the plan (and its captured graph) is reused when
         the random frame changes between sampling runs: only ``inject`` is rewritten.
         control: optional dict(output=[12 NHWC tensors], middle=NHWC tensor) produced by ControlNet.build for the same
-        (B,h,w): added to the skips / middle output as apply_control does (openaimodel.py:374-386, :899, :907)."""
+        (B,h,w): added to the skips / middle output as apply_control does (openaimodel.py:374-386, :899, :907).  A non-empty
+        control["input"] (one NHWC tensor or None per input block, from T2IAdapter.build) is added to the input blocks' outputs."""
         cfg, dt, dev = self.cfg, self.dtype, self.device
         pb = PlanBuilder(dev, dt)
         pro = PlanBuilder(dev, dt)                     # prompt-only work (cross-attention K/V)
@@ -379,6 +380,17 @@ class UNet:
         pb.nchw_to_nhwc(x_in, xh, B, cfg["in_channels"], h * w, cin_pad)
         cur = pb.buf(B, h * w, mc)
         pb.igemm(xh, W["input_blocks.0.0"], cur, B, h, w, cin_pad, mc, KH=3, bias=W["input_blocks.0.0.b"])
+        # T2I-Adapter features (control["input"], entry k for input block k): added after the block, before the skip is taken, so the
+        # sum feeds both the skip and the next block (apply_control(h, control, 'input'), openaimodel.py:891-897)
+        ctrl_in = list(control["input"]) if control is not None and control.get("input") else []
+
+        def input_control(x, k):
+            if k < len(ctrl_in) and ctrl_in[k] is not None:
+                y = pb.buf(*x.shape)
+                pb.add(x, ctrl_in[k], y)
+                return y
+            return x
+        cur = input_control(cur, 0)
         hs = [(cur, mc, h, w)]
         ch, hh, ww = mc, h, w
         td = list(cfg["transformer_depth"])
@@ -392,13 +404,14 @@ class UNet:
                 depth = td.pop(0)
                 if depth > 0:
                     cur = stransformer(f"input_blocks.{bi}.1", cur, ch, hh * ww, hh, ww, depth)
+                cur = input_control(cur, bi)
                 hs.append((cur, ch, hh, ww))
                 bi += 1
             if lev != nlev - 1:
                 ho, wo = (hh + 1) // 2, (ww + 1) // 2
                 dn = pb.buf(B, ho * wo, ch)
                 pb.igemm(cur, W[f"input_blocks.{bi}.0.op"], dn, B, hh, ww, ch, ch, KH=3, stride=2, bias=W[f"input_blocks.{bi}.0.op.b"])
-                cur, hh, ww = dn, ho, wo
+                cur, hh, ww = input_control(dn, bi), ho, wo
                 hs.append((cur, ch, hh, ww))
                 bi += 1
         # ---- middle ----------------------------------------------------------------------------------
@@ -410,7 +423,7 @@ class UNet:
             y = pb.buf(*x.shape)
             pb.add(x, c, y)
             return y
-        ctrl_out = list(control["output"]) if control is not None else None
+        ctrl_out = list(control["output"]) if control is not None and control.get("output") is not None else None
         if control is not None and control.get("middle") is not None:
             cur = add_control(cur, control["middle"])
         # ---- decoder ---------------------------------------------------------------------------------
