@@ -178,6 +178,9 @@ class CheckpointLoaderSimple:
                 vae = VAE(vae, VAEEncoder(vae_sd, dtype=dt, prefix="encoder."))
         if clip is None:
             clip = _NoCLIP()
+        w0 = unet_sd.get("input_blocks.0.0.weight")
+        if w0 is not None:                                       # an inpaint checkpoint is its family's UNet with a 9-channel input
+            cfg["in_channels"] = int(w0.shape[1])                # convolution (model_detection.py reads it off the same weight)
         model = N.MODEL(UNet(unet_sd, cfg, dtype=dt), state_dict=unet_sd, cfg=cfg, dtype=dt)
         return (model, clip if output_clip else None, vae)
 
@@ -1181,6 +1184,170 @@ class IfValTypeEqual(N.StableRenderingNode):
         return type(val).__name__.upper() == type_name.upper()
 
 
+# ---- inpainting ------------------------------------------------------------------------------------------------------------
+def _inpaint_inputs(pixels, mask, ratio=8):
+    """the head both inpaint nodes share (comfyUI/nodes.py:359-368, :406-416): the mask as (-1, 1, H, W), bilinear to the pixels' size,
+    and both cut to multiples of `ratio` around the centre -> (pixels view (B, x, y, C), mask view (M, 1, x, y)) on the device"""
+    from . import resample as RS
+    if pixels.dim() == 3:
+        pixels = pixels.unsqueeze(0)
+    pixels = pixels.to("cuda", torch.float32)
+    m = mask.reshape(-1, 1, mask.shape[-2], mask.shape[-1]).to("cuda", torch.float32)
+    m = RS.common_upscale(m, pixels.shape[2], pixels.shape[1], "bilinear", "disabled")
+    x, y = (pixels.shape[1] // ratio) * ratio, (pixels.shape[2] // ratio) * ratio
+    if pixels.shape[1] != x or pixels.shape[2] != y:
+        xo, yo = (pixels.shape[1] % ratio) // 2, (pixels.shape[2] % ratio) // 2
+        pixels, m = pixels[:, xo:x + xo, yo:y + yo, :], m[:, :, xo:x + xo, yo:y + yo]
+    return pixels, m
+
+
+class SetLatentNoiseMask:
+    """comfyUI/nodes.py:1380-1394: the sampler repaints where the mask is 1 and keeps the latent where it is 0"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "set_mask"
+    CATEGORY = "latent/inpaint"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "mask": ("MASK",)}}
+
+    def set_mask(self, samples, mask):
+        s = samples.copy()
+        s["noise_mask"] = mask.reshape((-1, 1, mask.shape[-2], mask.shape[-1]))
+        return (s,)
+
+
+class VAEEncodeForInpaint:
+    """comfyUI/nodes.py:349-386: the pixels under the (rounded) mask are set to 0.5 before encoding, and the latent carries the mask
+    grown by grow_mask_by pixels as its noise_mask (sr_inp_neutralise, sr_inp_grow)"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "encode"
+    CATEGORY = "latent/inpaint"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"pixels": ("IMAGE",), "vae": ("VAE",), "mask": ("MASK",),
+                             "grow_mask_by": ("INT", {"default": 6, "min": 0, "max": 64, "step": 1})}}
+
+    def encode(self, vae, pixels, mask, grow_mask_by=6):
+        from . import _inpaint as INP
+        pixels, m = _inpaint_inputs(pixels, mask, getattr(vae, "downscale_ratio", 8))
+        t = vae.encode(INP.neutralise(pixels, m)[:, :, :, :3])
+        return (N.LATENT(samples=t, noise_mask=INP.grow(m, grow_mask_by)),)
+
+
+class InpaintModelConditioning:
+    """comfyUI/nodes.py:389-441: for inpaint (9-channel) checkpoints.  The latent is the whole image's, its noise_mask the resized
+    mask unrounded; both conditionings get the neutralised image's latent and the mask as concat_latent_image / concat_mask, which
+    DiffusionRunner stages into the UNet's channels 4..8"""
+    RETURN_TYPES = ("CONDITIONING", "CONDITIONING", "LATENT")
+    RETURN_NAMES = ("positive", "negative", "latent")
+    FUNCTION = "encode"
+    CATEGORY = "conditioning/inpaint"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"positive": ("CONDITIONING",), "negative": ("CONDITIONING",), "vae": ("VAE",), "pixels": ("IMAGE",),
+                             "mask": ("MASK",)}}
+
+    def encode(self, positive, negative, pixels, vae, mask):
+        from . import _inpaint as INP
+        if pixels.dim() == 3:
+            pixels = pixels.unsqueeze(0)
+        cropped, m = _inpaint_inputs(pixels, mask)
+        m = m.contiguous()
+        concat_latent = vae.encode(INP.neutralise(cropped, m)[:, :, :, :3])
+        orig_latent = vae.encode(pixels[:, :, :, :3])
+        out = []
+        for conditioning in (positive, negative):
+            c = []
+            for t in conditioning:
+                d = t[1].copy()
+                d["concat_latent_image"] = concat_latent
+                d["concat_mask"] = m
+                c.append([t[0], d])
+            out.append(c)
+        return (out[0], out[1], N.LATENT(samples=orig_latent, noise_mask=m))
+
+
+class DifferentialDiffusion:
+    """comfy_extras/nodes_differential_diffusion.py: the noise mask becomes a per-pixel schedule -- at every evaluation it is cut at
+    the threshold (timestep - ts_to) / (ts_from - ts_to), so a pixel of mask value v is repainted during the first v of the run.  The
+    clone of the MODEL carries the flag; its runners apply the threshold in the blend kernels"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "apply"
+    CATEGORY = "_for_testing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",)}}
+
+    def apply(self, model):
+        m = N.MODEL(model.unet, state_dict=model.state_dict, cfg=model.cfg, dtype=model.dtype)
+        m.differential = True
+        return (m,)
+
+
+class LatentFromBatch:
+    """comfyUI/nodes.py:1108-1139: a batch of masks is repeated to the latent batch and cut with it, a single mask is kept"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "frombatch"
+    CATEGORY = "latent/batch"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "batch_index": ("INT", {"default": 0, "min": 0, "max": 63}),
+                             "length": ("INT", {"default": 1, "min": 1, "max": 64})}}
+
+    def frombatch(self, samples, batch_index, length):
+        import math
+        s = samples.copy()
+        s_in = samples["samples"]
+        batch_index = min(s_in.shape[0] - 1, batch_index)
+        length = min(s_in.shape[0] - batch_index, length)
+        s["samples"] = s_in[batch_index:batch_index + length].clone()
+        if "noise_mask" in samples:
+            masks = samples["noise_mask"]
+            if masks.shape[0] == 1:
+                s["noise_mask"] = masks.clone()
+            else:
+                if masks.shape[0] < s_in.shape[0]:
+                    masks = masks.repeat(math.ceil(s_in.shape[0] / masks.shape[0]), 1, 1, 1)[:s_in.shape[0]]
+                s["noise_mask"] = masks[batch_index:batch_index + length].clone()
+        if "batch_index" not in s:
+            s["batch_index"] = [x for x in range(batch_index, batch_index + length)]
+        else:
+            s["batch_index"] = samples["batch_index"][batch_index:batch_index + length]
+        return (s,)
+
+
+class RepeatLatentBatch:
+    """comfyUI/nodes.py:1141-1165.  As there, a batch of masks is repeated `amount` times as it came (the reference pads it to the
+    latent batch first and then repeats the unpadded one); a single mask is left alone and serves every item"""
+    RETURN_TYPES = ("LATENT",)
+    FUNCTION = "repeat"
+    CATEGORY = "latent/batch"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"samples": ("LATENT",), "amount": ("INT", {"default": 1, "min": 1, "max": 64})}}
+
+    def repeat(self, samples, amount):
+        s = samples.copy()
+        s["samples"] = samples["samples"].repeat((amount, 1, 1, 1))
+        if "noise_mask" in samples and samples["noise_mask"].shape[0] > 1:
+            s["noise_mask"] = samples["noise_mask"].repeat((amount, 1, 1, 1))
+        if "batch_index" in s:
+            offset = max(s["batch_index"]) - min(s["batch_index"]) + 1
+            s["batch_index"] = s["batch_index"] + [x + (i * offset) for i in range(1, amount) for x in s["batch_index"]]
+        return (s,)
+
+
+INPAINT_NODES = {"SetLatentNoiseMask": SetLatentNoiseMask, "VAEEncodeForInpaint": VAEEncodeForInpaint,
+                 "InpaintModelConditioning": InpaintModelConditioning, "DifferentialDiffusion": DifferentialDiffusion,
+                 "LatentFromBatch": LatentFromBatch, "RepeatLatentBatch": RepeatLatentBatch}
+
+
 for _name, _cls in (("CheckpointLoaderSimple", CheckpointLoaderSimple), ("LoraLoaderModelOnly", LoraLoaderModelOnly),
                     ("ControlNetLoader", ControlNetLoader), ("ControlNetApply", ControlNetApply), ("ControlNetApplyAdvanced", ControlNetApplyAdvanced), ("CLIPTextEncode", CLIPTextEncode),
                     ("SceneTextEncode", SceneTextEncode), ("MaskedTextEncode", MaskedTextEncode), ("KSampler", KSampler), ("VAEDecode", VAEDecode), ("VAEEncode", VAEEncode), ("VAEDecodeTiled", VAEDecodeTiled), ("VAEEncodeTiled", VAEEncodeTiled), ("LoadImage", LoadImage),
@@ -1215,6 +1382,9 @@ for _name, _cls in VAE_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in CLIP_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in INPAINT_NODES.items():
     register_node(_name, _cls)
 
 

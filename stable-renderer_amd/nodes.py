@@ -36,6 +36,7 @@ class MODEL:
         key = (N, h, w, float(cfg), use_graph, tuple((id(c), c.strength) for c in controlnets))
         if key not in self._runners:
             self._runners[key] = DiffusionRunner(self.unet, N, h, w, cfg, use_graph=use_graph, controlnets=list(controlnets))
+            self._runners[key].differential = bool(getattr(self, "differential", False))      # the DifferentialDiffusion node's flag
         return self._runners[key]
 
 
@@ -316,8 +317,9 @@ def custom_ksampler(model: MODEL, seed, steps, cfg, sampler_name, scheduler, pos
         def cb(ctx):
             for c in callbacks:
                 c(ctx)
+    masked = {"noise_mask": latent["noise_mask"]} if latent.get("noise_mask") is not None else {}       # nodes.py:1474-1476
     samples, inj = run.sample(noise, steps, sampler_name, scheduler, denoise=denoise, latent_image=latent_image, seed=seed,
-                              inject_n_rand=n_rand, step_callback=cb)
+                              inject_n_rand=n_rand, step_callback=cb, **masked)
     if inj is not None and corresponder is not None:
         corresponder._random_frame_indices = torch.tensor(inj)
     out = LATENT(latent)

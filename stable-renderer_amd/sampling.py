@@ -3,7 +3,9 @@ meaning: ``ModelSamplingDiscrete`` (comfyUI/comfy/model_sampling.py:75-150), ``c
 ``KSampler`` (comfy/samplers.py:415-451, 937-1078), ``calc_cond_uncond_batch`` + ``sampling_function`` (batch =
 [uncond | cond], CFG; samplers.py:176-358), ``BaseModel.apply_model`` with EPS scaling (comfy/model_base.py:93-127),
 the k-diffusion loops ``sample_euler`` / ``sample_ddpm`` / ``sample_lcm`` (comfy/k_diffusion/sampling.py:129-149,
-749-793; the eight further samplers of ksamplers.py are driven from here) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
+749-793; the eight further samplers of ksamplers.py are driven from here), ``KSamplerX0Inpaint`` with ``prepare_mask`` and
+``BaseModel.extra_conds`` for inpaint models (samplers.py:399-412, comfy/sample.py:40-46, model_base.py:136-185: masked sampling,
+_inpaint.py) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
 once on the host; everything per step (UNet plan, CFG, sampler update, latent overlap) runs as HIP kernels.
 """
 import math
@@ -174,6 +176,17 @@ class DiffusionRunner:
         if shard is not None and shard.active:
             assert N == shard.n_local
         self.unet, self.N, self.h, self.w = unet, N, h, w
+        # 4: the latent alone; 9: an inpaint UNet, whose channels 4..8 are c_concat = [mask | masked-image latent] (_load_concat)
+        self.cin = int(unet.cfg["in_channels"])
+        if self.cin not in (4, 9):
+            raise NotImplementedError(f"a UNet with in_channels = {self.cin} is not supported: 4 (latent) or 9 (inpaint: latent + mask + "
+                                      "masked-image latent)")
+        if self.cin == 9 and controlnets:
+            # their plans read the UNet plan's own input buffer (_build_controls), which then carries nine channels where a
+            # ControlNet's input convolution takes four
+            raise NotImplementedError("ControlNets / T2I-Adapters on a 9-channel inpaint UNet are not supported")
+        if self.cin == 9 and shard is not None and shard.active:
+            raise NotImplementedError("a 9-channel inpaint UNet on an active ViewShard is not supported")
         # ControlNets (comfy/controlnet.py:180-214 get_control, chained through previous_controlnet: residuals are summed,
         # control_merge :60-100); their plans read the UNet plan's own x / t / ctx buffers
         self.controlnets = list(controlnets or [])
@@ -194,6 +207,9 @@ class DiffusionRunner:
         self._stream = torch.cuda.Stream(device=dev) if use_graph else None
         self.time_comm, self._comm_events = False, []
         self._entries, self._general = None, None
+        self._inp = None                                    # the state of a masked run (_begin_masked), None outside one
+        self._concat = None                                 # (concat_latent_image, concat_mask) of the conditioning: 9-channel UNets
+        self.differential = False                           # DifferentialDiffusion: threshold the mask per evaluation (_masked_thr)
 
     def _ensure_plan(self, inject_idx):
         """the plan depends only on HOW MANY frames are injected; which ones is a device tensor rewritten per run"""
@@ -319,10 +335,17 @@ class DiffusionRunner:
     def set_cond_entries(self, positive, negative):
         """positive / negative: lists of conditioning entries (conditioning.entries_of): several prompts with masks, strengths
         and areas, composed as calc_cond_uncond_batch does (comfy/samplers.py:176-320).  One plain entry each is the ordinary
-        [uncond | cond] batch."""
+        [uncond | cond] batch.  An entry's concat_latent_image / concat_mask (InpaintModelConditioning) feed a 9-channel UNet."""
         from . import conditioning as CD
         CD.check_supported(positive)
         CD.check_supported(negative)
+        self._concat = None
+        if self.cin == 9:
+            src = [(e.get("concat_latent_image"), e.get("concat_mask")) for e in list(positive) + list(negative)]
+            if any(a is not src[0][0] or b is not src[0][1] for a, b in src[1:]):
+                raise NotImplementedError("conditioning entries with different concat_latent_image / concat_mask are not supported: "
+                                          "one c_concat serves the whole batch")
+            self._concat = src[0]
         if CD.is_plain(positive) and CD.is_plain(negative):
             self._entries = None
             return self.set_conditioning(positive[0]["cond"], negative[0]["cond"])
@@ -506,10 +529,57 @@ class DiffusionRunner:
                     hb[c * N:(c + 1) * N].copy_(hv.expand(N, -1, -1, -1) if hv.shape[0] == 1 else hv)
                 cp["prologue"].run()                        # hint encoder: once per run
 
+    @staticmethod
+    def _resize_to_batch_size(t, n):
+        """comfy.utils.resize_to_batch_size (utils.py:276-294): spread or thin the batch evenly -- not repeat_to_batch_size"""
+        m = t.shape[0]
+        if m == n:
+            return t
+        if n <= 1:
+            return t[:n]
+        if n < m:
+            idx = [min(round(i * ((m - 1) / (n - 1))), m - 1) for i in range(n)]
+        else:
+            idx = [min(math.floor((i + 0.5) * (m / n)), m - 1) for i in range(n)]
+        return t[torch.tensor(idx, device=t.device)]
+
+    def _load_concat(self, p, latent, mask):
+        """BaseModel.extra_conds of an inpaint model (comfy/model_base.py:136-185) -> channels 4..8 of the plan's input, once per run:
+        the conditioning's concat_latent_image (through process_latent_in) and concat_mask; failing those the run's scaled
+        latent_image and prepared mask; failing a mask altogether a ones mask and the latent of a blank image.  The UNet input is
+        cat([x / sqrt(sigma^2 + 1), c_concat]): c_concat is not scaled (apply_model), so the steps leave these channels alone."""
+        from . import _inpaint as INP
+        from . import resample as RS
+        N, h, w, dev = self.N, self.h, self.w, self.x.device
+        cl, cm = self._concat if self._concat is not None else (None, None)
+        cl = latent if cl is None else cl.to(dev, torch.float32) * self.latent_scale
+        if tuple(cl.shape[1:]) != (4, h, w):
+            cl = RS.common_upscale(cl, w, h, "bilinear", "center")
+        cl = self._resize_to_batch_size(cl, N).contiguous()
+        if cm is not None:
+            cm = cm.to(dev, torch.float32)
+            if cm.dim() == 4:
+                cm = cm[:, :1]
+            cm = cm.reshape(-1, 1, cm.shape[-2], cm.shape[-1])
+            if tuple(cm.shape[-2:]) != (h, w):
+                cm = RS.common_upscale(cm, w, h, "bilinear", "center")
+            cm = self._resize_to_batch_size(cm, N)
+        elif mask is not None:
+            cm = mask                                       # (M, 1, h, w): the kernel's n % M is prepare_mask's repeat to the batch
+        else:
+            cm = torch.ones(1, 1, h, w, dtype=torch.float32, device=dev)
+            # "zero" in pixel space translated to latent space (blank_inpaint_image_like)
+            cl = torch.tensor([0.8223, -0.6876, 0.6364, 0.1380], dtype=torch.float32, device=dev).view(1, 4, 1, 1).expand(N, 4, h, w).contiguous()
+        INP.concat(cm, cl, p["x"], self.copies)
+
     def model_eps(self, p, sigma, timestep_index, x=None):
         """calc_cond_uncond_batch + apply_model: xin = x/sqrt(sigma^2+1) for both chunks, t = argmin|log sigma|"""
         n = self.x.numel()
-        O.eps_scale_input(self.x if x is None else x, p["x"], self.copies, sigma)
+        if self.cin == 4:
+            O.eps_scale_input(self.x if x is None else x, p["x"], self.copies, sigma)
+        else:                                               # the latent's four channels of a wider input; c_concat is in the others
+            from . import _inpaint as INP
+            INP.stage(self.x if x is None else x, p["x"], self.copies, sigma)
         p["t"].fill_(float(timestep_index))
         if p.get("cn") is not None:                         # ControlNet encoders on the same (x, t, ctx), then their merge; no
             self._run_controls(p, sigma)                    # cross-view work inside them (controlnet.py:205-213 passes no corresponder)
@@ -586,6 +656,51 @@ class DiffusionRunner:
         self._comm_events = []
         return ms
 
+    def _prepare_mask(self, noise_mask):
+        """comfy.sample.prepare_mask (sample.py:40-46): (-1, 1, H, W), bilinear to the latent's size -> (M, 1, h, w) on the device.
+        Its copies per channel and per batch item are not made: the blend kernels read mask[n % M] (repeat_to_batch_size)"""
+        from . import resample as RS
+        m = noise_mask.reshape(-1, 1, noise_mask.shape[-2], noise_mask.shape[-1]).to(self.x.device, torch.float32)
+        if m.shape[0] == 0:
+            raise ValueError("noise_mask is empty")
+        return RS.common_upscale(m, self.w, self.h, "bilinear", "disabled")
+
+    def _begin_masked(self, noise_mask, noise, latent, sig):
+        """the state of a masked run (KSAMPLER.sample, samplers.py:764-772): the prepared mask, the unscaled noise and the scaled
+        latent_image stay resident; xm is the latent the model sees.  differential: DifferentialDiffusion's threshold range"""
+        ts = None
+        if self.differential:
+            s_to = max(float(self.ms.sigma_min), float(sig[-1]))
+            ts = (int(self.ms.timestep(float(sig[0]))), int(self.ms.timestep(s_to)))
+        ws = getattr(self, "_inp_xm", None)
+        if ws is None:
+            ws = self._inp_xm = torch.empty_like(self.x)
+        self._inp = dict(mask=self._prepare_mask(noise_mask), noise=noise, latent=latent, xm=ws, ts=ts)
+
+    def _masked_thr(self, t_idx):
+        """DifferentialDiffusion.forward (nodes_differential_diffusion.py:20-34): (ts - ts_to) / (ts_from - ts_to) on integer tensors
+        is ONE fp32 division of the two converted integers; None without the flag"""
+        ts = self._inp["ts"]
+        if ts is None:
+            return None
+        import numpy as np
+        return float(np.float32(t_idx - ts[1]) / np.float32(ts[0] - ts[1]))
+
+    def _masked_eval(self, p, x, sigma, t_idx, den, d):
+        """KSamplerX0Inpaint.forward (samplers.py:399-412) around one evaluation: blend the known region into a workspace latent at
+        this sigma, evaluate on it as ever, blend the known region back into den; d = (x - den) / sigma is k-diffusion's to_d on what
+        the wrapper returns, with the sampler's own x.  p: the plan of the plain path, None = the general path"""
+        from . import _inpaint as INP
+        I = self._inp
+        thr = self._masked_thr(t_idx)
+        INP.blend_in(x, I["noise"], I["latent"], I["mask"], sigma, I["xm"], thr=thr)
+        if p is None:
+            self._general_denoise(sigma, t_idx, False, x=I["xm"], den=den)
+        else:
+            eps = self.model_eps(p, sigma, t_idx, x=I["xm"])
+            O.cfg_denoise(I["xm"], eps, den, None, self.copies, sigma, self.cfg_scale)
+        INP.blend_out(den, I["latent"], I["mask"], thr=thr, x=x if d is not None else None, d=d, sigma=sigma)
+
     def _run_ksampler(self, sampler, ks, p, noise_fn, predrawn, step_callback, pre_step_callback):
         """the loop of one of ksamplers.py's samplers over this runner: self.x is the latent, `evaluate` is the model call plus CFG
         on any latent at any sigma (timestep, ControlNets and, on the general path, the active entries of THAT sigma), slot 0 is
@@ -603,7 +718,9 @@ class DiffusionRunner:
                 if pre_step_callback is not None:
                     pre_step_callback(self.x, state["step"], ks.timesteps[state["step"]])
             t_idx = int(self.ms.timestep(sigma))
-            if p is None:
+            if self._inp is not None:                           # masked: the model sees the blended latent, x itself survives
+                self._masked_eval(p, x, sigma, t_idx, den, d)
+            elif p is None:
                 self._general_denoise(sigma, t_idx, True, x=x, den=den, d=d)
             else:
                 eps = self.model_eps(p, sigma, t_idx, x=x)
@@ -620,7 +737,7 @@ class DiffusionRunner:
         KS.DRIVERS[sampler](evaluate, noise_fn, self.x, sig, callback if step_callback is not None else None, ws)
 
     def sample(self, noise, steps, sampler_name, scheduler, denoise=1.0, latent_image=None, seed=None,
-               inject_n_rand=None, step_callback=None, noise_fn=None, rng_turn=None, pre_step_callback=None):
+               inject_n_rand=None, step_callback=None, noise_fn=None, rng_turn=None, pre_step_callback=None, noise_mask=None):
         """-> samples (N,4,h,w) fp32 on device (already divided by the latent scale, samplers.py:933).
 
         RNG draw order on the *global CPU generator* replicates the reference: custom_ksampler's seed draw
@@ -628,7 +745,13 @@ class DiffusionRunner:
         on the first attention block (corresponder.py:204-205), then the sampler's per-step randn_like.
 
         pre_step_callback(x, i, timestep): called before the model evaluation of step i with the step's input latent (the
-        evaluation only reads it) -- the view-sharded pipeline starts the latent all-gather of the step's overlap here."""
+        evaluation only reads it) -- the view-sharded pipeline starts the latent all-gather of the step's overlap here.
+
+        noise_mask: a latent's "noise_mask" (any (..., H, W) mask; 1 = repaint, 0 = keep latent_image): every model evaluation is
+        then wrapped in the two blends of KSamplerX0Inpaint (_masked_eval); None launches exactly what it always did."""
+        if noise_mask is not None and self.shard is not None and self.shard.active:
+            raise NotImplementedError("noise_mask on an active ViewShard is not supported: masked (inpaint) sampling runs unsharded")
+        self._inp = None
         ks = KSampler(steps, sampler_name, scheduler, denoise, self.ms)
         sig = ks.sigmas
         sampler = ks.sampler_name
@@ -679,13 +802,20 @@ class DiffusionRunner:
         max_denoise = math.isclose(float(self.ms.sigma_max), float(sig[0]), rel_tol=1e-05) or float(sig[0]) > float(self.ms.sigma_max)
         s0 = float(torch.sqrt(1.0 + sig[0] ** 2.0)) if max_denoise else float(sig[0])
         self.x.copy_(noise.to(dev, torch.float32))
-        O.axpby(self.x, latent.to(dev, torch.float32).contiguous(), 1.0, s0)        # x = noise*s0 + latent
+        latent = latent.to(dev, torch.float32).contiguous()
+        O.axpby(self.x, latent, 1.0, s0)                                             # x = noise*s0 + latent
+        if noise_mask is not None:
+            self._begin_masked(noise_mask, noise.to(dev, torch.float32).contiguous(), latent, sig)
+        if general and self.cin != 4:
+            raise NotImplementedError("conditioning lists (areas, masks, several entries) with a 9-channel inpaint UNet are not supported")
         if general:
             self._general_plans(inject, [float(v) for v in sig[:-1]] + (KS.extra_sigmas(sampler, sig) if sampler in KS.DRIVERS else []))
             p = G["groups"][0]["plan"]
         else:
             p = self._ensure_plan(inject)
             self._load_ctx(p)
+            if self.cin == 9:
+                self._load_concat(p, latent, self._inp["mask"] if self._inp is not None else None)
         if noise_fn is None and predrawn is not None:
             def noise_fn():
                 return predrawn.pop(0).to(dev)
@@ -699,7 +829,9 @@ class DiffusionRunner:
             s, sn = float(sig[i]), float(sig[i + 1])
             if pre_step_callback is not None:
                 pre_step_callback(self.x, i, ks.timesteps[i])
-            if general:
+            if self._inp is not None:
+                self._masked_eval(None if general else p, self.x, s, t_index[i], self.den, self.d if sampler in ("euler", "ddim") else None)
+            elif general:
                 self._general_denoise(s, t_index[i], sampler in ("euler", "ddim"))
             else:
                 eps = self.model_eps(p, s, t_index[i])
@@ -714,6 +846,7 @@ class DiffusionRunner:
                 O.lcm_step(self.x, self.den, noise_fn() if sn > 0 else None, sn)
             else:
                 raise ValueError(sampler)
+        self._inp = None                                    # (the mask, the noise and the latent image of the run are released)
         out = torch.empty_like(self.x)
         out.zero_()
         O.axpby(out, self.x, 1.0 / self.latent_scale, 0.0)
