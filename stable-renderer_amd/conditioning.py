@@ -44,7 +44,9 @@ def check_supported(entries):
 
 
 def percent_to_sigma(ms, percent):
-    """ModelSamplingDiscrete.percent_to_sigma (comfy/model_sampling.py:138-144)"""
+    """ModelSamplingDiscrete.percent_to_sigma (comfy/model_sampling.py:138-144); a model-sampling object of guidance.py has its own"""
+    if hasattr(ms, "percent_to_sigma"):
+        return ms.percent_to_sigma(percent)
     if percent <= 0.0:
         return 999999999.9
     if percent >= 1.0:

@@ -22,7 +22,8 @@ models).  names() and the three older tables are pinned by tests, so all_names()
 PRIVATE_EXTRA is the fifth table of the same form and the open-ended one: all_names() and the four older tables are pinned by tests,
 so every later private library joins this table (libsr_canny.so is the first, libsr_taesd.so, the TAESD tiny autoencoder, the
 second, libsr_compact.so, the Real-ESRGAN compact upscale models, the third, libsr_clip.so, the CLIP text encoder, the fourth, libsr_t2i.so, the
-T2I-Adapter control network, the fifth, libsr_inpaint.so, masked (inpaint) sampling, the sixth), and no test pins its length or its full content.
+T2I-Adapter control network, the fifth, libsr_inpaint.so, masked (inpaint) sampling, the sixth,
+libsr_guidance.so, model sampling and guidance, the seventh), and no test pins its length or its full content.
 every_name() = all_names() + this table is what builds everything.
 
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
@@ -61,6 +62,7 @@ PRIVATE_EXTRA = {
     "clip": ("clip", "clip.hip", "sr_clip.h", "SR_CLIP_SRC_HASH"),
     "t2i": ("t2i", "t2i.hip", "sr_t2i.h", "SR_T2I_SRC_HASH"),
     "inpaint": ("inpaint", "inpaint.hip", "sr_inpaint.h", "SR_INPAINT_SRC_HASH"),
+    "guidance": ("guidance", "guidance.hip", "sr_guidance.h", "SR_GUIDANCE_SRC_HASH"),
 }
 
 

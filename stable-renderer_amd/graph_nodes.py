@@ -181,7 +181,19 @@ class CheckpointLoaderSimple:
         w0 = unet_sd.get("input_blocks.0.0.weight")
         if w0 is not None:                                       # an inpaint checkpoint is its family's UNet with a 9-channel input
             cfg["in_channels"] = int(w0.shape[1])                # convolution (model_detection.py reads it off the same weight)
+        if "edm_mean" in r and "edm_std" in r:                   # supported_models.py:166-171 (Playground v2.5)
+            raise NotImplementedError("a checkpoint with edm_mean / edm_std (Playground v2.5: EDM sampling with sigma_data 0.5 and a "
+                                      "latent format of its own) is not supported")
+        wk = unet_sd.get("input_blocks.1.1.transformer_blocks.0.attn2.to_k.weight")
+        if wk is not None and not cfg.get("adm_in_channels") and int(wk.shape[1]) == 1024:
+            raise NotImplementedError("SD2.x checkpoints are not supported: their ViT-H text encoder and the v-prediction detection "
+                                      "(the std of an output bias above 0.09) are not built")
+        v_pred = "v_pred" in r or "v_pred" in unet_sd            # (a top-level key of the file; a provider may leave it with the UNet)
+        unet_sd = {k: v for k, v in unet_sd.items() if k != "v_pred"} if "v_pred" in unet_sd else unet_sd
         model = N.MODEL(UNet(unet_sd, cfg, dtype=dt), state_dict=unet_sd, cfg=cfg, dtype=dt)
+        if cfg.get("adm_in_channels") and v_pred:                # supported_models.py:172-173: an SDXL file that declares v-prediction
+            from . import guidance as GDH
+            model.patches = GDH.ModelPatches(model_sampling=GDH.ModelSamplingDiscrete("v_prediction"))
         return (model, clip if output_clip else None, vae)
 
 
@@ -205,7 +217,7 @@ class LoraLoaderModelOnly:
         lora = WT.resolve("loras", lora_name)
         km = WT.unet_lora_key_map(model.cfg, model.state_dict.keys())
         sd, unused = WT.apply_lora(model.state_dict, lora, float(strength_model), km)
-        m = N.MODEL(UNet(sd, model.cfg, dtype=model.dtype), state_dict=sd, cfg=model.cfg, dtype=model.dtype)
+        m = model.clone(unet=UNet(sd, model.cfg, dtype=model.dtype), state_dict=sd)      # (keeps the patches of the model it is given)
         m.lora_unused_keys = unused
         return (m,)
 
@@ -1283,7 +1295,7 @@ class DifferentialDiffusion:
         return {"required": {"model": ("MODEL",)}}
 
     def apply(self, model):
-        m = N.MODEL(model.unet, state_dict=model.state_dict, cfg=model.cfg, dtype=model.dtype)
+        m = model.clone()
         m.differential = True
         return (m,)
 
@@ -1348,6 +1360,110 @@ INPAINT_NODES = {"SetLatentNoiseMask": SetLatentNoiseMask, "VAEEncodeForInpaint"
                  "LatentFromBatch": LatentFromBatch, "RepeatLatentBatch": RepeatLatentBatch}
 
 
+# ---- model sampling and guidance (comfy_extras/nodes_model_advanced.py) -----------------------------------------------------
+def _patched_clone(model, **kw):
+    """model.clone() with one of its patches replaced (add_object_patch / set_model_sampler_cfg_function on the clone)"""
+    from . import guidance as GDH
+    m = model.clone()
+    m.patches = (model.patches if model.patches is not None else GDH.ModelPatches()).replace(**kw)
+    return m
+
+
+class ModelSamplingDiscrete:
+    """nodes_model_advanced.py:72-107: the discrete schedule with another parameterisation (lcm: the distilled 50-sigma schedule),
+    zsnr: its sigmas rescaled to a zero terminal SNR"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "patch"
+    CATEGORY = "advanced/model"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",),
+                             "sampling": (["eps", "v_prediction", "lcm", "x0"],),
+                             "zsnr": ("BOOLEAN", {"default": False})}}
+
+    def patch(self, model, sampling, zsnr):
+        from . import guidance as GDH
+        if sampling == "lcm":
+            ms = GDH.ModelSamplingDiscreteDistilled("lcm", zsnr=zsnr)
+        elif sampling in ("eps", "v_prediction", "x0"):
+            ms = GDH.ModelSamplingDiscrete(sampling, zsnr=zsnr)
+        else:
+            raise ValueError(f"ModelSamplingDiscrete: sampling '{sampling}' is none of eps, v_prediction, lcm, x0")
+        return (_patched_clone(model, model_sampling=ms),)
+
+
+class ModelSamplingContinuousEDM:
+    """nodes_model_advanced.py:135-171: 1000 log-spaced sigmas between sigma_min and sigma_max, a continuous timestep"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "patch"
+    CATEGORY = "advanced/model"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",),
+                             "sampling": (["v_prediction", "edm_playground_v2.5", "eps"],),
+                             "sigma_max": ("FLOAT", {"default": 120.0, "min": 0.0, "max": 1000.0, "step": 0.001, "round": False}),
+                             "sigma_min": ("FLOAT", {"default": 0.002, "min": 0.0, "max": 1000.0, "step": 0.001, "round": False})}}
+
+    def patch(self, model, sampling, sigma_max, sigma_min):
+        from . import guidance as GDH
+        if sampling == "edm_playground_v2.5":
+            raise NotImplementedError("ModelSamplingContinuousEDM: sampling 'edm_playground_v2.5' is not supported: it needs sigma_data "
+                                      "0.5 and a latent-format patch (SDXL_Playground_2_5)")
+        if sampling not in ("v_prediction", "eps"):
+            raise ValueError(f"ModelSamplingContinuousEDM: sampling '{sampling}' is none of v_prediction, edm_playground_v2.5, eps")
+        return (_patched_clone(model, model_sampling=GDH.ModelSamplingContinuousEDM(sampling, sigma_min, sigma_max, 1.0)),)
+
+
+class ModelSamplingStableCascade:
+    """nodes_model_advanced.py:109-133: refused by name (the cosine schedule of a model family that is not built)"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "patch"
+    CATEGORY = "advanced/model"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",), "shift": ("FLOAT", {"default": 2.0, "min": 0.0, "max": 100.0, "step": 0.01})}}
+
+    def patch(self, model, shift):
+        raise NotImplementedError("ModelSamplingStableCascade is not supported: Stable Cascade models are not built")
+
+
+class RescaleCFG:
+    """nodes_model_advanced.py:173-210: guidance in v-space, rescaled to the standard deviation of the positive prediction"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "patch"
+    CATEGORY = "advanced/model"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",),
+                             "multiplier": ("FLOAT", {"default": 0.7, "min": 0.0, "max": 1.0, "step": 0.01})}}
+
+    def patch(self, model, multiplier):
+        return (_patched_clone(model, cfg_function=("rescale", float(multiplier))),)
+
+
+class PerpNeg:
+    """comfy_extras/nodes_perpneg.py: refused by name (its cfg function evaluates a third, empty conditioning)"""
+    RETURN_TYPES = ("MODEL",)
+    FUNCTION = "patch"
+    CATEGORY = "_for_testing"
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"model": ("MODEL",), "empty_conditioning": ("CONDITIONING",),
+                             "neg_scale": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 100.0})}}
+
+    def patch(self, model, empty_conditioning, neg_scale):
+        raise NotImplementedError("PerpNeg is not supported: its cfg function needs a third model evaluation per step")
+
+
+GUIDANCE_NODES = {"ModelSamplingDiscrete": ModelSamplingDiscrete, "ModelSamplingContinuousEDM": ModelSamplingContinuousEDM,
+                  "ModelSamplingStableCascade": ModelSamplingStableCascade, "RescaleCFG": RescaleCFG, "PerpNeg": PerpNeg}
+
+
 for _name, _cls in (("CheckpointLoaderSimple", CheckpointLoaderSimple), ("LoraLoaderModelOnly", LoraLoaderModelOnly),
                     ("ControlNetLoader", ControlNetLoader), ("ControlNetApply", ControlNetApply), ("ControlNetApplyAdvanced", ControlNetApplyAdvanced), ("CLIPTextEncode", CLIPTextEncode),
                     ("SceneTextEncode", SceneTextEncode), ("MaskedTextEncode", MaskedTextEncode), ("KSampler", KSampler), ("VAEDecode", VAEDecode), ("VAEEncode", VAEEncode), ("VAEDecodeTiled", VAEDecodeTiled), ("VAEEncodeTiled", VAEEncodeTiled), ("LoadImage", LoadImage),
@@ -1385,6 +1501,9 @@ for _name, _cls in CLIP_NODES.items():
     register_node(_name, _cls)
 
 for _name, _cls in INPAINT_NODES.items():
+    register_node(_name, _cls)
+
+for _name, _cls in GUIDANCE_NODES.items():
     register_node(_name, _cls)
 
 

@@ -31,11 +31,26 @@ class MODEL:
         self.cfg = cfg if cfg is not None else unet.cfg
         self.dtype = dtype if dtype is not None else unet.dtype
         self._runners = {}
+        self.patches = None                                 # guidance.ModelPatches of the patch nodes; None: an unpatched model
+
+    def clone(self, unet=None, state_dict=None):
+        """ModelPatcher.clone: the same UNet (or, for a LoRA, re-packed weights) under a MODEL of its own that carries this one's
+        patches and DifferentialDiffusion's flag, with runners of its own; a patch node changes the clone, never its input"""
+        m = MODEL(self.unet if unet is None else unet, state_dict=self.state_dict if state_dict is None else state_dict, cfg=self.cfg,
+                  dtype=self.dtype)
+        m.patches = self.patches
+        if getattr(self, "differential", False):
+            m.differential = True
+        return m
 
     def runner(self, N, h, w, cfg, use_graph=True, controlnets=()):
         key = (N, h, w, float(cfg), use_graph, tuple((id(c), c.strength) for c in controlnets))
+        patched = {}
+        if self.patches is not None and self.patches.any:
+            key += (self.patches.key(),)
+            patched = dict(model_sampling=self.patches.model_sampling, cfg_function=self.patches.cfg_function)
         if key not in self._runners:
-            self._runners[key] = DiffusionRunner(self.unet, N, h, w, cfg, use_graph=use_graph, controlnets=list(controlnets))
+            self._runners[key] = DiffusionRunner(self.unet, N, h, w, cfg, use_graph=use_graph, controlnets=list(controlnets), **patched)
             self._runners[key].differential = bool(getattr(self, "differential", False))      # the DifferentialDiffusion node's flag
         return self._runners[key]
 

@@ -5,7 +5,8 @@ meaning: ``ModelSamplingDiscrete`` (comfyUI/comfy/model_sampling.py:75-150), ``c
 the k-diffusion loops ``sample_euler`` / ``sample_ddpm`` / ``sample_lcm`` (comfy/k_diffusion/sampling.py:129-149,
 749-793; the eight further samplers of ksamplers.py are driven from here), ``KSamplerX0Inpaint`` with ``prepare_mask`` and
 ``BaseModel.extra_conds`` for inpaint models (samplers.py:399-412, comfy/sample.py:40-46, model_base.py:136-185: masked sampling,
-_inpaint.py) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
+_inpaint.py), the two hooks of a patched MODEL, ``model_sampling`` and ``sampler_cfg_function`` (samplers.py:346-351, guidance.py,
+_guidance.py) and ``custom_ksampler`` (comfyUI/nodes.py:1438-1495).  The sigma schedule is a few hundred scalars computed
 once on the host; everything per step (UNet plan, CFG, sampler update, latent overlap) runs as HIP kernels.
 """
 import math
@@ -133,6 +134,13 @@ class SamplingCallbackContext:
         return self.sigmas[self.step_index]
 
 
+def timestep_of(ms, sigma):
+    """ms.timestep(sigma) as the plan's t buffer takes it: the integer index of a discrete schedule, the fractional timestep of a
+    continuous one (ModelSamplingContinuousEDM: 0.25 * ln sigma, -inf at the schedule's final 0) as a float"""
+    t = ms.timestep(sigma)
+    return float(t) if torch.is_floating_point(t) else int(t)
+
+
 class KSampler:
     """Schedule holder (comfy/samplers.py:954-1003).  ``timesteps`` is NOT re-sliced when denoise < 1, exactly as in
     the reference (samplers.py:1000-1003 vs types/runtime.py:585-588).  A name outside the reference's list falls back to
@@ -157,7 +165,7 @@ class KSampler:
         the sigma before the final 0; the timesteps keep it, as there"""
         discard = self.sampler_name in KS.DISCARD_PENULTIMATE_SIGMA
         sig = calculate_sigmas_scheduler(self.ms, self.scheduler, steps + 1 if discard else steps)
-        timesteps = [int(self.ms.timestep(s)) for s in sig]
+        timesteps = [timestep_of(self.ms, s) for s in sig]
         if discard:
             sig = torch.cat([sig[:-2], sig[-1:]])
         return sig, timesteps
@@ -169,10 +177,23 @@ class DiffusionRunner:
     ``sample()`` is the body of custom_ksampler -> comfy.sample.sample -> KSampler.sample -> sampler loop with the
     model call replaced by the native plan; the latent stays resident in HBM for the whole run."""
 
-    def __init__(self, unet, N, h, w, cfg_scale, n_ctx=77, use_graph=True, shard=None, controlnets=None):
+    def __init__(self, unet, N, h, w, cfg_scale, n_ctx=77, use_graph=True, shard=None, controlnets=None, model_sampling=None,
+                 cfg_function=None):
         """shard: optional parallel.ViewShard — this process then holds ``shard.n_local`` of the ``shard.n_views`` views of ONE
-        overlapped group; N must equal shard.n_local."""
+        overlapped group; N must equal shard.n_local.
+
+        model_sampling: a model-sampling object of guidance.py (the MODEL's "model_sampling" patch: schedule + parameterisation);
+        cfg_function: ("rescale", multiplier), RescaleCFG in place of plain guidance (the "sampler_cfg_function" patch).  With
+        either, a model output becomes the denoised latent through _guidance.py's kernels (_cfg_denoise, _guide); with neither the
+        launches, their order and the bits are what they always were and that library is not loaded."""
         self.shard = shard
+        if model_sampling is not None or cfg_function is not None:
+            from . import guidance as GDH
+            GDH.check_cfg_function(cfg_function)
+            if model_sampling is not None:
+                GDH.check_model_sampling(model_sampling)
+            if shard is not None and shard.active:
+                raise NotImplementedError("model_sampling / cfg_function patches on an active ViewShard are not supported")
         if shard is not None and shard.active:
             assert N == shard.n_local
         self.unet, self.N, self.h, self.w = unet, N, h, w
@@ -196,7 +217,10 @@ class DiffusionRunner:
         self.n_ctx = n_ctx
         self.use_graph = use_graph
         self.graph_segments = _GRAPH_SEGMENTS               # view shard: replay the cut plan segments as hipGraphs (see _sharded_eval)
-        self.ms = ModelSamplingDiscrete()
+        self.ms = model_sampling if model_sampling is not None else ModelSamplingDiscrete()
+        self.cfg_function = cfg_function
+        self._gd = None                                     # the workspace of the patched path (_guidance_state), None unpatched
+        self._patched = model_sampling is not None or cfg_function is not None
         self.latent_scale = latent_scale_of(unet.cfg)   # process_latent_in / process_latent_out (samplers.py:905, :933)
         self._plan = None
         self._inject = "unset"
@@ -491,9 +515,17 @@ class DiffusionRunner:
                 self._sharded_eval(p, chunks=g["chunks"])
             else:
                 p["step"].run()
-            O.cond_accumulate(x, p["out"], g["mult"], g["kinds"], G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], g["area"],
-                              g["chunks"], sigma)
-        O.cfg_combine(x, G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], den, d if want_d else None, sigma, self.cfg_scale)
+            if self._patched:
+                gd = self._guidance_state()
+                gd["GD"].accumulate(x, p["out"], g["mult"], g["kinds"], G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], g["area"],
+                                    g["chunks"], gd["param"], sigma, 1.0, float(timestep_index), contract=gd["contract"])
+            else:
+                O.cond_accumulate(x, p["out"], g["mult"], g["kinds"], G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], g["area"],
+                                  g["chunks"], sigma)
+        if self._patched:
+            self._guide(G["out_c"], G["out_u"], x, den, d if want_d else None, sigma, cnt_c=G["cnt_c"], cnt_u=G["cnt_u"])
+        else:
+            O.cfg_combine(x, G["out_c"], G["cnt_c"], G["out_u"], G["cnt_u"], den, d if want_d else None, sigma, self.cfg_scale)
 
     def _load_ctx(self, p):
         N = self.N
@@ -656,6 +688,36 @@ class DiffusionRunner:
         self._comm_events = []
         return ms
 
+    def _guidance_state(self):
+        """the patched path's workspace: the two denoised chunks and RescaleCFG's (N, 4) double sums; the library loads here"""
+        if self._gd is None:
+            from . import _guidance as GD
+            from . import guidance as GDH
+            param = GDH.param_code(self.ms)
+            # an eps model sampling is the reference's no-op patch: its x - out * sigma and the plain guidance after it are asked for in
+            # the fused form sr_cfg_denoise / sr_cond_accumulate / sr_cfg_combine are compiled to, so that it is a no-op here too
+            self._gd = dict(GD=GD, param=param, contract=param == GDH.PARAM_CODES["eps"], den_u=torch.empty_like(self.x), den_c=torch.empty_like(self.x),
+                            ws=torch.empty(self.N, 4, dtype=torch.float64, device=self.x.device))
+        return self._gd
+
+    def _guide(self, a_c, a_u, x, den, d, sigma, cnt_c=None, cnt_u=None):
+        """sampling_function after the model calls (samplers.py:346-351): plain guidance, or the MODEL's cfg function"""
+        gd = self._guidance_state()
+        if self.cfg_function is None:
+            gd["GD"].cfg(a_c, a_u, x, den, d, sigma, self.cfg_scale, cnt_c=cnt_c, cnt_u=cnt_u, contract=gd["contract"])
+        else:
+            gd["GD"].rescale(a_c, a_u, x, den, d, gd["ws"], sigma, self.cfg_scale, self.cfg_function[1], cnt_c=cnt_c, cnt_u=cnt_u)
+
+    def _cfg_denoise(self, x, out, den, d, sigma, t_idx):
+        """the plain path after the model call: calculate_denoised per chunk, then guidance.  Unpatched it is sr_cfg_denoise, one
+        launch; patched, sr_gd_denoise under the model sampling's parameterisation and sr_gd_cfg / sr_gd_rescale.  At cfg 1 the
+        uncond chunk is not evaluated and the cfg function sees uncond_denoised = 0 (samplers.py:335)"""
+        if not self._patched:
+            return O.cfg_denoise(x, out, den, d, self.copies, sigma, self.cfg_scale)
+        gd = self._guidance_state()
+        gd["GD"].denoise(x, out, gd["den_u"], gd["den_c"], self.copies, gd["param"], sigma, 1.0, float(t_idx), contract=gd["contract"])
+        self._guide(gd["den_c"], gd["den_u"] if self.copies == 2 else None, x, den, d, sigma)
+
     def _prepare_mask(self, noise_mask):
         """comfy.sample.prepare_mask (sample.py:40-46): (-1, 1, H, W), bilinear to the latent's size -> (M, 1, h, w) on the device.
         Its copies per channel and per batch item are not made: the blend kernels read mask[n % M] (repeat_to_batch_size)"""
@@ -671,7 +733,7 @@ class DiffusionRunner:
         ts = None
         if self.differential:
             s_to = max(float(self.ms.sigma_min), float(sig[-1]))
-            ts = (int(self.ms.timestep(float(sig[0]))), int(self.ms.timestep(s_to)))
+            ts = (timestep_of(self.ms, float(sig[0])), timestep_of(self.ms, s_to))
         ws = getattr(self, "_inp_xm", None)
         if ws is None:
             ws = self._inp_xm = torch.empty_like(self.x)
@@ -698,7 +760,7 @@ class DiffusionRunner:
             self._general_denoise(sigma, t_idx, False, x=I["xm"], den=den)
         else:
             eps = self.model_eps(p, sigma, t_idx, x=I["xm"])
-            O.cfg_denoise(I["xm"], eps, den, None, self.copies, sigma, self.cfg_scale)
+            self._cfg_denoise(I["xm"], eps, den, None, sigma, t_idx)
         INP.blend_out(den, I["latent"], I["mask"], thr=thr, x=x if d is not None else None, d=d, sigma=sigma)
 
     def _run_ksampler(self, sampler, ks, p, noise_fn, predrawn, step_callback, pre_step_callback):
@@ -717,14 +779,14 @@ class DiffusionRunner:
                 state["step"] += 1
                 if pre_step_callback is not None:
                     pre_step_callback(self.x, state["step"], ks.timesteps[state["step"]])
-            t_idx = int(self.ms.timestep(sigma))
+            t_idx = timestep_of(self.ms, sigma)
             if self._inp is not None:                           # masked: the model sees the blended latent, x itself survives
                 self._masked_eval(p, x, sigma, t_idx, den, d)
             elif p is None:
                 self._general_denoise(sigma, t_idx, True, x=x, den=den, d=d)
             else:
                 eps = self.model_eps(p, sigma, t_idx, x=x)
-                O.cfg_denoise(x, eps, den, d, self.copies, sigma, self.cfg_scale)
+                self._cfg_denoise(x, eps, den, d, sigma, t_idx)
             return den, d
 
         def callback(i, x, den):
@@ -822,7 +884,7 @@ class DiffusionRunner:
         elif noise_fn is None:
             def noise_fn():
                 return torch.randn(tuple(self.x.shape), dtype=torch.float32).to(dev)    # default_noise_sampler (CPU x)
-        t_index = [int(t) for t in self.ms.timestep(sig[:-1])]          # ModelSamplingDiscrete.timestep, once per run
+        t_index = [timestep_of(self.ms, t) for t in sig[:-1]]           # model_sampling.timestep, once per run
         if sampler in KS.DRIVERS:
             self._run_ksampler(sampler, ks, p if not general else None, noise_fn, predrawn, step_callback, pre_step_callback)
         for i in range(len(sig) - 1) if sampler not in KS.DRIVERS else ():
@@ -835,7 +897,7 @@ class DiffusionRunner:
                 self._general_denoise(s, t_index[i], sampler in ("euler", "ddim"))
             else:
                 eps = self.model_eps(p, s, t_index[i])
-                O.cfg_denoise(self.x, eps, self.den, self.d if sampler in ("euler", "ddim") else None, self.copies, s, self.cfg_scale)
+                self._cfg_denoise(self.x, eps, self.den, self.d if sampler in ("euler", "ddim") else None, s, t_index[i])
             if step_callback is not None:
                 step_callback(SamplingCallbackContext(self.x, i, self.den, len(sig) - 1, ks.timesteps, sig.tolist()))
             if sampler in ("euler", "ddim"):
