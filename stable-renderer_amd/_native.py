@@ -1,5 +1,5 @@
 """The one loader of the native libraries: libsr_hip.so (csrc/build.py, bound by _lib.py) and the side libraries of
-csrc/sidelib.py (bound by _lib_tiled.py, _lib_resample.py, _lib_imgproc.py).  A library must have been built from the sources lying
+csrc/sidelib.py (each bound by the module sidelib.binding(name) names).  A library must have been built from the sources lying
 next to it: a missing or stale one is rebuilt when hipcc is there and refused otherwise -- it is never loaded silently (a stale .so
 was tested once: commit e818dd3), and there is no CPU fallback."""
 import ctypes as C

@@ -19,37 +19,11 @@ import re
 
 import torch
 
-from .esrgan import MAX_ELEMS, unwrap
+# The packed weight layout is the ESRGAN library's (csrc/conv3_pack.h): sr_cmp_packed_index states the same index.
+from .esrgan import MAX_ELEMS, _pad32, pack_weight, packed_index, unpack_weight, unwrap  # noqa: F401
 
 ARCH = "SRVGG (RealESRGAN)"
 _BODY = re.compile(r"body\.(\d+)\.(weight|bias)$")
-
-
-def packed_index(Cout, Cin, n, c, ky, kx):
-    """sr_cmp_packed_index (sr_compact.h), restated"""
-    frag = (((c // 32) * 9 + ky * 3 + kx) * 2 + (c % 32) // 16) * (Cout // 32) + n // 32
-    return frag * 512 + (((c % 16) // 8) * 32 + n % 32) * 8 + c % 8
-
-
-def pack_weight(w, cin_pad=None, cout_pad=None):
-    """(Cout, Cin, 3, 3) -> the flat fp16 array of sr_compact.h, channels zero-padded to (cout_pad, cin_pad)"""
-    co, ci = w.shape[:2]
-    cop, cip = cout_pad or co, cin_pad or ci
-    if tuple(w.shape[2:]) != (3, 3) or cop % 32 or cip % 32 or cop < co or cip < ci:
-        raise ValueError(f"pack_weight: a {tuple(w.shape)} weight into ({cop}, {cip}, 3, 3)")
-    full = torch.zeros(cop, cip, 9, dtype=torch.float16)
-    full[:co, :ci] = w.reshape(co, ci, 9).to(torch.float16)
-    # n -> (nt, nr), c -> (cc, ks, hh, j), tap  ->  [cc][tap][ks][nt][hh][nr][j]
-    return full.reshape(cop // 32, 32, cip // 32, 2, 2, 8, 9).permute(2, 6, 3, 0, 4, 1, 5).contiguous().reshape(-1)
-
-
-def unpack_weight(packed, Cout, Cin):
-    """the inverse of pack_weight -> (Cout, Cin, 3, 3) fp16"""
-    return packed.reshape(Cin // 32, 9, 2, Cout // 32, 2, 32, 8).permute(3, 5, 0, 2, 4, 6, 1).reshape(Cout, Cin, 3, 3)
-
-
-def _pad32(n):
-    return (n + 31) // 32 * 32
 
 
 def check_conv(L, i=0):

@@ -23,6 +23,7 @@
 #define SR_ESRGAN_SRC_HASH "unstamped"
 #endif
 #include "../sr_side.h"
+#include "../conv3_pack.h"
 
 namespace {
 
@@ -210,9 +211,7 @@ int check_layer(const sr_esr_conv& L, int i) {
 }  // namespace
 
 extern "C" int64_t sr_esr_packed_index(int32_t Cout, int32_t Cin, int32_t n, int32_t c, int32_t ky, int32_t kx) {
-  if (Cout < 32 || Cout % 32 || Cin < 32 || Cin % 32 || n < 0 || n >= Cout || c < 0 || c >= Cin || ky < 0 || ky > 2 || kx < 0 || kx > 2) return -1;
-  const int64_t frag = ((int64_t)((c / 32) * 9 + ky * 3 + kx) * 2 + (c % 32) / 16) * (Cout / 32) + n / 32;
-  return frag * 512 + (((c % 16) / 8) * 32 + n % 32) * 8 + c % 8;
+  return conv3_packed_index(Cout, Cin, n, c, ky, kx);
 }
 
 extern "C" int sr_esr_run(const sr_esr_conv* layers, int32_t n, void* stream) {

@@ -1,30 +1,15 @@
-"""Build the side libraries for gfx950 with hipcc: libsr_tiled.so (the tiled VAE), libsr_resample.so (common_upscale) and
-libsr_imgproc.so (the image and mask filters).  Each is one translation unit, linked in-tree next to its source under a private
-name and renamed, and carries the hash of its sources (sr_<name>_source_hash).
+"""Build the side libraries for gfx950 with hipcc: csrc/<name>/libsr_<name>.so, one translation unit each, linked in-tree next to
+its source under a private name and renamed, carrying the hash of its sources (sr_<name>_source_hash).
 
 Why they are libraries of their own: bench.py's recorded frame checksum and the recorded igemm traffic are stamped with the source
-hash of libsr_hip.so (csrc/build.py).  These are bandwidth-bound helpers around its launch plans; kept out of its source list,
-they leave that identity, and the records with it, alone.  For the same reason this file loads csrc/build.py for hipcc() instead
-of touching it, and sr_side.h, not sr_common.h, is their shared prologue.
+hash of libsr_hip.so (csrc/build.py).  Kept out of its source list, these leave that identity, and the records with it, alone.  For
+the same reason this file loads csrc/build.py for hipcc() instead of touching it, and sr_side.h, not sr_common.h, is their prologue.
 
-A new side library is one entry here, one .hip, one header under include/ and one SYMBOLS table bound by _native.SideLibrary.
-
-PRIVATE holds the side libraries whose ABI only this package calls (no call site in the reference, nothing for INTEGRATION.md to
-describe): their header lies next to the source, not under include/, and their binding module is not named _lib_*.py.  They are
-built, hashed and loaded by the same rules; every function here resolves a name in either table.
-
-PRIVATE_NODES is a third table of the same form as PRIVATE, for the private libraries behind graph nodes (libsr_morph.so: Morphology
-and Porter-Duff compositing).  It exists because the contents of the two older tables are pinned by tests; names() lists all three.
-
-PRIVATE_MODELS is a fourth table of the same form, for the private libraries that run a whole model (libsr_esrgan.so: the upscale
-models).  names() and the three older tables are pinned by tests, so all_names() = names() + this table.
-
-PRIVATE_EXTRA is the fifth table of the same form and the open-ended one: all_names() and the four older tables are pinned by tests,
-so every later private library joins this table (libsr_canny.so is the first, libsr_taesd.so, the TAESD tiny autoencoder, the
-second, libsr_compact.so, the Real-ESRGAN compact upscale models, the third, libsr_clip.so, the CLIP text encoder, the fourth, libsr_t2i.so, the
-T2I-Adapter control network, the fifth, libsr_inpaint.so, masked (inpaint) sampling, the sixth,
-libsr_guidance.so, model sampling and guidance, the seventh), and no test pins its length or its full content.
-every_name() = all_names() + this table is what builds everything.
+A new side library is one entry in LIBRARIES, one csrc/<name>/<name>.hip (which names itself with SR_SIDE / SR_SIDE_UC and gives
+SR_<NAME>_SRC_HASH a default), one header sr_<name>.h and one binding module with a SYMBOLS table for _native.SideLibrary.  A public
+library's ABI is described in INTEGRATION.md: its header lies under include/ and _lib_<name>.py binds it.  A private one has one
+caller, this package: its header lies next to the source and _<name>.py binds it.  `shared` lists further headers under csrc/ that
+the source includes; every file that reaches the compiler must be named here, or a stale library would pass for a current one.
 
     python stable-renderer_amd/csrc/sidelib.py [name ...] [--force]"""
 import hashlib
@@ -36,63 +21,35 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"]
 SHARED = "sr_side.h"
-# name -> (directory, source, public header under include/, hash macro)
-REGISTRY = {
-    "tiled": ("tiled", "tiled.hip", "sr_tiled.h", "SR_TILED_SRC_HASH"),
-    "resample": ("resample", "resample.hip", "sr_resample.h", "SR_RESAMPLE_SRC_HASH"),
-    "imgproc": ("imgproc", "imgproc.hip", "sr_imgproc.h", "SR_IMGPROC_SRC_HASH"),
-}
-# name -> (directory, source, private header next to the source, hash macro)
-PRIVATE = {
-    "ksteps": ("ksteps", "ksteps.hip", "sr_ksteps.h", "SR_KSTEPS_SRC_HASH"),
-}
-# name -> (directory, source, private header next to the source, hash macro)
-PRIVATE_NODES = {
-    "morph": ("morph", "morph.hip", "sr_morph.h", "SR_MORPH_SRC_HASH"),
-}
-# name -> (directory, source, private header next to the source, hash macro)
-PRIVATE_MODELS = {
-    "esrgan": ("esrgan", "esrgan.hip", "sr_esrgan.h", "SR_ESRGAN_SRC_HASH"),
-}
-# name -> (directory, source, private header next to the source, hash macro); later private libraries join this table
-PRIVATE_EXTRA = {
-    "canny": ("canny", "canny.hip", "sr_canny.h", "SR_CANNY_SRC_HASH"),
-    "taesd": ("taesd", "taesd.hip", "sr_taesd.h", "SR_TAESD_SRC_HASH"),
-    "compact": ("compact", "compact.hip", "sr_compact.h", "SR_COMPACT_SRC_HASH"),
-    "clip": ("clip", "clip.hip", "sr_clip.h", "SR_CLIP_SRC_HASH"),
-    "t2i": ("t2i", "t2i.hip", "sr_t2i.h", "SR_T2I_SRC_HASH"),
-    "inpaint": ("inpaint", "inpaint.hip", "sr_inpaint.h", "SR_INPAINT_SRC_HASH"),
-    "guidance": ("guidance", "guidance.hip", "sr_guidance.h", "SR_GUIDANCE_SRC_HASH"),
+CONV3 = ("conv3_pack.h",)         # the packed weight layout of the patch-stationary 3x3 convolutions
+# name -> what cannot be derived from the name, in build order
+LIBRARIES = {
+    "tiled": dict(public=True), "resample": dict(public=True), "imgproc": dict(public=True),
+    "ksteps": dict(public=False), "morph": dict(public=False), "esrgan": dict(public=False, shared=CONV3),
+    "canny": dict(public=False), "taesd": dict(public=False, shared=CONV3), "compact": dict(public=False, shared=CONV3),
+    "clip": dict(public=False), "t2i": dict(public=False), "inpaint": dict(public=False), "guidance": dict(public=False),
 }
 
 
 def names():
-    """every side library: the three tables' names, in order"""
-    return list(REGISTRY) + list(PRIVATE) + list(PRIVATE_NODES)
-
-
-def all_names():
-    """names() and the model libraries of PRIVATE_MODELS"""
-    return names() + list(PRIVATE_MODELS)
-
-
-def every_name():
-    """all_names() and the libraries of PRIVATE_EXTRA: everything sidelib builds"""
-    return all_names() + list(PRIVATE_EXTRA)
+    return list(LIBRARIES)
 
 
 def entry(name):
-    """-> (directory, source, path of the header, hash macro) of a public or a private side library"""
-    if name in REGISTRY:
-        d, src, hdr, macro = REGISTRY[name]
-        return d, src, os.path.join(HERE, "..", "..", "include", hdr), macro
-    for table in (PRIVATE, PRIVATE_NODES, PRIVATE_MODELS, PRIVATE_EXTRA):
-        if name in table:
-            d, src, hdr, macro = table[name]
-            break
-    else:
-        raise KeyError(name)
-    return d, src, os.path.join(HERE, d, hdr), macro
+    """-> (directory, source, path of the header, hash macro); KeyError for an unknown name"""
+    hdr = os.path.join(HERE, "..", "..", "include") if LIBRARIES[name]["public"] else os.path.join(HERE, name)
+    return name, name + ".hip", os.path.join(hdr, "sr_%s.h" % name), "SR_%s_SRC_HASH" % name.upper()
+
+
+def binding(name):
+    """the module of the package that binds the library"""
+    return ("_lib_" if LIBRARIES[name]["public"] else "_") + name
+
+
+def sources(name):
+    """every file of the repository the compiler reads for this library"""
+    d, src, hdr, _ = entry(name)
+    return [os.path.join(HERE, d, src), hdr, os.path.join(HERE, SHARED)] + [os.path.join(HERE, s) for s in LIBRARIES[name].get("shared", ())]
 
 
 def lib_path(name):
@@ -100,10 +57,9 @@ def lib_path(name):
 
 
 def source_hash(name):
-    """sha256 over the source, its header (wherever it lies), the shared prologue and this file (the flags live here)"""
-    d, src, hdr, _ = entry(name)
-    h = hashlib.sha256()
-    for fp in (os.path.join(HERE, d, src), hdr, os.path.join(HERE, SHARED), os.path.abspath(__file__)):
+    """sha256 over sources(name) and the compile flags"""
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for fp in sources(name):
         h.update(os.path.basename(fp).encode())
         with open(fp, "rb") as fh:
             h.update(fh.read())
@@ -141,5 +97,5 @@ def build(name, force=False):
 
 
 if __name__ == "__main__":
-    for n in [a for a in sys.argv[1:] if a != "--force"] or every_name():
+    for n in [a for a in sys.argv[1:] if a != "--force"] or names():
         print(build(n, force="--force" in sys.argv))

@@ -1,6 +1,6 @@
 """Host half of Canny edge detection: the integer restatement of cv2.Canny (tests/canny_ref.py) against the reference's recorded edge
 images (tests/golden/canny_cv.npz, tools/gen_golden_canny.py), the float detector's envelope oracle and its two conditions, the
-private side library libsr_canny.so (header == table, the open-ended fifth table of csrc/sidelib.py, bad arguments refused before any
+private side library libsr_canny.so (header == table, bad arguments refused before any
 launch), the Canny node's declarations against the reference class's recorded ones, and the wrappers' argument errors.  No GPU."""
 import ctypes as C
 import json
@@ -107,26 +107,6 @@ def test_header_declares_exactly_the_symbol_table(tmp_path):
     assert (v["SR_CANNY_NONE"], v["SR_CANNY_WEAK"], v["SR_CANNY_STRONG"]) == (0, 1, 2) and v["SR_CANNY_TILE"] == 64
 
 
-def test_open_table_resolves_canny_and_every_name_extends_all_names():
-    from stable_renderer_amd import _canny as LC, _native
-    sidelib = _native.sidelib()
-    assert "canny" in sidelib.PRIVATE_EXTRA and "canny" not in sidelib.all_names()
-    every = sidelib.every_name()
-    assert every[:len(sidelib.all_names())] == sidelib.all_names() and "canny" in every and len(set(every)) == len(every)
-    assert "PRIVATE_EXTRA" in sidelib.__doc__ and "joins this table" in sidelib.__doc__
-    d, src, hdr, macro = sidelib.entry("canny")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_CANNY_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert LC.LIB_PATH == sidelib.lib_path("canny") == os.path.join(_native.CSRC, "canny", "libsr_canny.so")
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_canny.py"))
-    with open(os.path.join(_native.CSRC, d, src)) as f:
-        text = f.read()
-    assert "#define SR_SIDE canny\n" in text and "#define SR_SIDE_UC CANNY\n" in text and '"sr_canny.h"' in text and '"../sr_side.h"' in text
-    hashes = [sidelib.source_hash(n) for n in every]
-    assert all(len(h) == 32 for h in hashes) and len(set(hashes)) == len(hashes)
-    with pytest.raises(KeyError):
-        sidelib.entry("no_such_library")
-
-
 def test_library_resolves_every_symbol_and_refuses_bad_arguments():
     from stable_renderer_amd import _canny as LC
     L = LC.lib()                                               # raises if the .so is missing, stale or lacks a symbol of SYMBOLS
@@ -171,13 +151,6 @@ def test_library_resolves_every_symbol_and_refuses_bad_arguments():
     assert fin(one, 8, one, 2, 1) == -1 and b"unknown out_dtype 2" in err()
     assert fin(one, 8, one, 0, 3) == -1 and b"c_out = 3" in err()
     assert fin(one, 8, one, 1, 5) == -1 and b"c_out = 5" in err()
-
-
-def test_entry_builds_every_name():
-    """build() and sidelib's command line go through every_name(): a library of the open table is built with the rest"""
-    with open(os.path.join(ROOT, "__graft_entry__.py")) as f:
-        text = f.read()
-    assert text.count("side.every_name()") == 2 and "all_names()" not in text
 
 
 # ---- the node and the wrappers ------------------------------------------------------------------------------------------------------

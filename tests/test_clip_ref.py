@@ -1,7 +1,7 @@
 """Host half of the native CLIP text encoder: the tokenizer (stable_renderer_amd.clip_tokenizer) against the reference's recorded output
 (tests/golden/clip_tokens.json.gz, tools/gen_golden_clip.py), the float64 restatement (tests/clip_ref.py) against the reference's own
 outputs (tests/golden/clip.npz, clip_wide.npz), key conversion, refusals, the private side library libsr_clip.so (header == table ==
-ctypes mirror, bad descriptors refused before any launch), the open registry table, the packed weight layout, the launch list, the
+ctypes mirror, bad descriptors refused before any launch), the encoder's source, the packed weight layout, the launch list, the
 nodes' declarations and the lazy CLIP of CheckpointLoaderSimple.  No GPU."""
 import gzip
 import json
@@ -373,21 +373,12 @@ def test_library_refuses_bad_descriptors_before_any_launch():
         assert emb(**kw) == -1 and text in err(), (kw, err())
 
 
-def test_open_table_resolves_clip():
-    from stable_renderer_amd import _clip as K, _native
-    sidelib = _native.sidelib()
-    assert "clip" in sidelib.PRIVATE_EXTRA and "clip" not in sidelib.all_names() and "clip" in sidelib.every_name()
-    assert len(set(sidelib.every_name())) == len(sidelib.every_name()) >= 10           # with libsr_hip.so: eleven libraries
-    d, src, hdr, macro = sidelib.entry("clip")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_CLIP_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert K.LIB_PATH == sidelib.lib_path("clip") == os.path.join(_native.CSRC, "clip", "libsr_clip.so")
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_clip.py")) and "libsr_clip.so" in sidelib.__doc__
-    with open(os.path.join(_native.CSRC, d, src)) as f:
+def test_encoder_source_is_mfma_and_stays_clear_of_the_main_library():
+    from stable_renderer_amd import _native
+    with open(os.path.join(_native.CSRC, "clip", "clip.hip")) as f:
         text = f.read()
-    assert "#define SR_SIDE clip\n" in text and "#define SR_SIDE_UC CLIP\n" in text and '"sr_clip.h"' in text and '"../sr_side.h"' in text
     assert "sr_common.h" not in text and "__builtin_amdgcn_mfma_f32_32x32x16_f16" in text and "hipMalloc" not in text
     assert "atomic" not in text.replace("no atomics", "")
-    assert sidelib.source_hash("clip") not in [sidelib.source_hash(n) for n in sidelib.every_name() if n != "clip"]
     # the encoder goes through neither the plan executor, the igemm tuner nor attention.hip
     for mod in ("clip.py", "_clip.py", "clip_tokenizer.py"):
         with open(os.path.join(ROOT, "stable-renderer_amd", mod)) as f:

@@ -1,7 +1,7 @@
 """Host half of the Real-ESRGAN compact upscale models: the float64 restatement (tests/compact_ref.py) against the reference's own
 outputs (tests/golden/compact.npz, tools/gen_golden_compact.py), the key parsing of stable_renderer_amd.compact against what the
 reference derived, the refusals, the dispatch of esrgan.load_upscale_model, the private side library libsr_compact.so (header ==
-table == ctypes mirror, bad arguments refused before any launch), the open registry table, the packed weight layout, the launch list
+table == ctypes mirror, bad arguments refused before any launch), the kernel's text, the packed weight layout, the launch list
 and a small graph through build_prompt.  No GPU."""
 import os
 
@@ -291,25 +291,12 @@ def test_library_refuses_bad_arguments_before_any_launch():
     assert pack(p, 1, 1, 1, 1, 1 << 10, 1 << 10, 1 << 10, 3, p, 32) == -1 and b"2^31" in err()
 
 
-def test_open_table_resolves_compact():
-    from stable_renderer_amd import _compact as K, _native
-    sidelib = _native.sidelib()
-    assert "compact" in sidelib.PRIVATE_EXTRA and "compact" not in sidelib.all_names() and "compact" in sidelib.every_name()
-    assert len(set(sidelib.every_name())) == len(sidelib.every_name()) >= 9           # with libsr_hip.so: ten libraries
-    d, src, hdr, macro = sidelib.entry("compact")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_COMPACT_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert K.LIB_PATH == sidelib.lib_path("compact") == os.path.join(_native.CSRC, "compact", "libsr_compact.so")
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_compact.py"))
-    assert "libsr_compact.so" in sidelib.__doc__
-    with open(os.path.join(_native.CSRC, d, src)) as f:
+def test_kernel_text_is_mfma_without_atomics_allocation_or_fmaxf():
+    from stable_renderer_amd import _native
+    with open(os.path.join(_native.CSRC, "compact", "compact.hip")) as f:
         text = f.read()
-    assert "#define SR_SIDE compact\n" in text and "#define SR_SIDE_UC COMPACT\n" in text and '"sr_compact.h"' in text and '"../sr_side.h"' in text
     assert "__builtin_amdgcn_mfma_f32_32x32x16_f16" in text and "atomic" not in text.replace("no atomics", "") and "hipMalloc" not in text
     assert "fmaxf" not in text                                  # the PReLU is a select, never max(v, slope v)
-    assert sidelib.source_hash("compact") not in [sidelib.source_hash(n) for n in sidelib.every_name() if n != "compact"]
-    # esrgan.hip and taesd.hip are left alone: the kernels share no file but the common prologue
-    for other in ("esrgan", "taesd"):
-        assert "compact" not in open(os.path.join(_native.CSRC, other, other + ".hip")).read()
 
 
 # ---- the nodes -----------------------------------------------------------------------------------------------------------------------

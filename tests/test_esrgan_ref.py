@@ -1,7 +1,7 @@
 """Host half of the ESRGAN upscale models: the float64 restatement (tests/esrgan_ref.py) against the reference's own outputs
 (tests/golden/esrgan.npz, tools/gen_golden_esrgan.py), the key parsing of stable_renderer_amd.esrgan against what the reference derived,
 the refusals, the private side library libsr_esrgan.so (header == table == ctypes mirror, bad arguments refused before any launch),
-the fourth registry table, the nodes' declarations, a small graph through build_prompt, the packed weight layout and the tile
+the nodes' declarations, a small graph through build_prompt, the packed weight layout and the tile
 schedule.  No GPU."""
 import ctypes as C
 import json
@@ -220,25 +220,6 @@ def test_library_refuses_bad_arguments_before_any_launch():
     assert pack(p, 1, 1, 1, 1, 1, 1, 8, 3, 2, p, 32) == -1 and b"reflect padding" in err()
     assert pack(p, 1, 1, 1, 1, 1, 8, 8, 3, 4, p, 32) == -1 and b"hold 48 channels" in err()
     assert pack(p, 1, 1, 1, 1, 1, 8, 8, 3, 1, p, 36) == -1 and b"ld_dst = 36" in err()
-
-
-def test_fourth_table_resolves_and_names_is_unchanged():
-    from stable_renderer_amd import _esrgan as LE, _native
-    sidelib = _native.sidelib()
-    assert tuple(sidelib.PRIVATE_MODELS) == ("esrgan",)
-    assert sidelib.names() == ["tiled", "resample", "imgproc", "ksteps", "morph"]
-    assert sidelib.all_names() == sidelib.names() + ["esrgan"] and len(sidelib.all_names()) == 6
-    d, src, hdr, macro = sidelib.entry("esrgan")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_ESRGAN_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert LE.LIB_PATH == sidelib.lib_path("esrgan") == os.path.join(_native.CSRC, "esrgan", "libsr_esrgan.so")
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_esrgan.py"))
-    with pytest.raises(KeyError):
-        sidelib.entry("nothing")
-    with open(os.path.join(_native.CSRC, d, src)) as f:
-        text = f.read()
-    assert "#define SR_SIDE esrgan\n" in text and "#define SR_SIDE_UC ESRGAN\n" in text and '"sr_esrgan.h"' in text and '"../sr_side.h"' in text
-    hashes = [sidelib.source_hash(n) for n in sidelib.all_names()]
-    assert all(len(h) == 32 for h in hashes) and len(set(hashes)) == len(hashes)
 
 
 # ---- packed weights --------------------------------------------------------------------------------------------------------------------

@@ -286,7 +286,7 @@ def test_side_library_is_registered_and_private():
     import re
     from stable_renderer_amd import _guidance, _native
     sl = _native.sidelib()
-    assert "guidance" in sl.PRIVATE_EXTRA and "guidance" in sl.every_name() and "guidance" not in sl.all_names()
+    assert "guidance" in sl.names() and sl.binding("guidance") == "_guidance"
     d, src, hdr, macro = sl.entry("guidance")
     assert os.path.exists(os.path.join(sl.HERE, d, src)) and os.path.dirname(hdr).endswith("guidance") and macro == "SR_GUIDANCE_SRC_HASH"
     with open(hdr) as f:

@@ -114,7 +114,7 @@ def test_goldens_hold_the_cases_the_gpu_test_runs(fix):
 def test_side_library_is_registered_and_private():
     from stable_renderer_amd import _native
     sl = _native.sidelib()
-    assert "inpaint" in sl.PRIVATE_EXTRA and "inpaint" in sl.every_name() and "inpaint" not in sl.all_names()
+    assert "inpaint" in sl.names() and sl.binding("inpaint") == "_inpaint"
     d, src, hdr, macro = sl.entry("inpaint")
     assert os.path.exists(os.path.join(sl.HERE, d, src)) and os.path.dirname(hdr).endswith("inpaint") and macro == "SR_INPAINT_SRC_HASH"
     with open(hdr) as f:

@@ -178,25 +178,6 @@ def test_no_cpu_fallback_without_the_library(monkeypatch):
         side.lib()
 
 
-def test_third_table_resolves_and_names_lists_all_three():
-    from stable_renderer_amd import _morph as LM, _native
-    sidelib = _native.sidelib()
-    assert tuple(sidelib.PRIVATE_NODES) == ("morph",)
-    assert sidelib.names() == list(sidelib.REGISTRY) + list(sidelib.PRIVATE) + list(sidelib.PRIVATE_NODES)
-    assert sidelib.names() == ["tiled", "resample", "imgproc", "ksteps", "morph"]
-    d, src, hdr, macro = sidelib.entry("morph")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_MORPH_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert LM.LIB_PATH == sidelib.lib_path("morph") == os.path.join(_native.CSRC, "morph", "libsr_morph.so")
-    assert os.path.samefile(sidelib.entry("ksteps")[2], os.path.join(_native.CSRC, "ksteps", "sr_ksteps.h"))
-    assert os.path.samefile(sidelib.entry("tiled")[2], os.path.join(ROOT, "include", "sr_tiled.h"))
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_morph.py"))
-    with open(os.path.join(_native.CSRC, d, src)) as f:
-        text = f.read()
-    assert "#define SR_SIDE morph\n" in text and "#define SR_SIDE_UC MORPH\n" in text and '"sr_morph.h"' in text and '"../sr_side.h"' in text
-    hashes = [sidelib.source_hash(n) for n in sidelib.names()]
-    assert all(len(h) == 32 for h in hashes) and len(set(hashes)) == len(hashes)
-
-
 # ---- nodes ---------------------------------------------------------------------------------------------------------------------------
 
 def _plain(v):

@@ -180,21 +180,6 @@ def test_no_cpu_fallback_without_the_library(monkeypatch):
         side.lib()
 
 
-def test_private_library_stays_out_of_the_public_sets():
-    from stable_renderer_amd import _ksteps as LK, _native
-    sidelib = _native.sidelib()
-    assert tuple(sidelib.REGISTRY) == ("tiled", "resample", "imgproc") and tuple(sidelib.PRIVATE) == ("ksteps",)
-    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == ["sr_hip.h", "sr_imgproc.h", "sr_resample.h", "sr_tiled.h"]
-    d, src, hdr, macro = sidelib.entry("ksteps")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_KSTEPS_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert LK.LIB_PATH == sidelib.lib_path("ksteps") == os.path.join(_native.CSRC, "ksteps", "libsr_ksteps.so")
-    assert os.path.samefile(sidelib.entry("tiled")[2], os.path.join(ROOT, "include", "sr_tiled.h"))
-    with open(os.path.join(_native.CSRC, d, src)) as f:
-        text = f.read()
-    assert "#define SR_SIDE ksteps\n" in text and "#define SR_SIDE_UC KSTEPS\n" in text and '"sr_ksteps.h"' in text
-    assert len(sidelib.source_hash("ksteps")) == 32 and sidelib.source_hash("ksteps") != sidelib.source_hash("tiled")
-
-
 # ---- names -----------------------------------------------------------------------------------------------------------------------
 
 def test_sampler_names_are_the_reference_list(fix):

@@ -1,7 +1,6 @@
 """Host half of the TAESD tiny autoencoder: the float64 restatement of both networks (tests/taesd_ref.py) against the reference's
 recorded outputs (tests/golden/taesd.npz, tools/gen_golden_taesd.py), the loader's validation, the launch list held against the
-restatement layer by layer on the CPU, the private side library libsr_taesd.so (header == table == ctypes mirror, the open table of
-csrc/sidelib.py, bad arguments refused before any launch), the packed weight layout, VAELoader's declarations and name resolution
+restatement layer by layer on the CPU, the private side library libsr_taesd.so (header == table == ctypes mirror, bad arguments refused before any launch), the packed weight layout, VAELoader's declarations and name resolution
 against the reference class's recorded ones.  No GPU."""
 import ctypes as C
 import json
@@ -195,22 +194,11 @@ def test_header_declares_exactly_the_symbol_table(tmp_path):
     assert (v["SR_TAESD_OK"], v["SR_TAESD_ERR_INVALID"], v["SR_TAESD_ERR_LAUNCH"]) == (0, -1, -2) and v["SR_TAE_MAX_LAYERS"] == 256
 
 
-def test_open_table_resolves_taesd():
-    from stable_renderer_amd import _taesd as LT, _native
-    sidelib = _native.sidelib()
-    assert "taesd" in sidelib.PRIVATE_EXTRA and "taesd" not in sidelib.all_names() and "taesd" in sidelib.every_name()
-    assert len(set(sidelib.every_name())) == len(sidelib.every_name()) >= 8           # with libsr_hip.so: nine libraries
-    d, src, hdr, macro = sidelib.entry("taesd")
-    assert os.path.samefile(hdr, HEADER) and macro == "SR_TAESD_SRC_HASH" and os.path.exists(os.path.join(_native.CSRC, d, src))
-    assert LT.LIB_PATH == sidelib.lib_path("taesd") == os.path.join(_native.CSRC, "taesd", "libsr_taesd.so")
-    assert not os.path.exists(os.path.join(ROOT, "stable-renderer_amd", "_lib_taesd.py"))
-    with open(os.path.join(_native.CSRC, d, src)) as f:
+def test_kernel_text_is_mfma_without_atomics_or_allocation():
+    from stable_renderer_amd import _native
+    with open(os.path.join(_native.CSRC, "taesd", "taesd.hip")) as f:
         text = f.read()
-    assert "#define SR_SIDE taesd\n" in text and "#define SR_SIDE_UC TAESD\n" in text and '"sr_taesd.h"' in text and '"../sr_side.h"' in text
     assert "__builtin_amdgcn_mfma_f32_32x32x16_f16" in text and "atomic" not in text.replace("no atomics", "") and "hipMalloc" not in text
-    assert sidelib.source_hash("taesd") not in [sidelib.source_hash(n) for n in sidelib.every_name() if n != "taesd"]
-    # esrgan.hip is left alone: the two kernels share no file but the common prologue
-    assert "taesd" not in open(os.path.join(_native.CSRC, "esrgan", "esrgan.hip")).read()
 
 
 def _conv(LT, **kw):
